@@ -48,7 +48,13 @@ def parse():
     ap.add_argument("--no-graph", action="store_true", help="skip the eager-vs-graph A/B regions (profiling passes)")
     ap.add_argument("--secondary-budget", type=float, default=420.0,
                     help="seconds the secondary regions may take in total before the line is printed without the rest")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (render_rays' dict, rank 0) "
+                         "as DIR/<name>.npy in float32; above 64 MB in all, a fixed seeded sample of the rays")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def spawn_ranks(args):
@@ -70,6 +76,25 @@ def spawn_ranks(args):
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
     raise SystemExit(subprocess.run(cmd, env=env).returncode)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(ret, out_dir, n_rays, seed=0):
+    """render_rays' dict -> out_dir/<key>.npy (float32).  Every entry is per ray (leading dimension n_rays); when the
+    whole dict is over DUMP_LIMIT_BYTES, the same seeded sample of rays (sorted indices) is kept in every entry."""
+    arrays = {k: v.detach().float().contiguous().cpu() for k, v in ret.items() if torch.is_tensor(v)}
+    total = sum(a.numel() * 4 for a in arrays.values())
+    room = DUMP_LIMIT_BYTES - 4096 * len(arrays)          # (the .npy headers)
+    if total > room:
+        keep = max(1, n_rays * room // total)
+        idx = torch.randperm(n_rays, generator=torch.Generator().manual_seed(seed))[:keep].sort().values
+        arrays = {k: a[idx] for k, a in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    import numpy as np
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a.numpy())
 
 
 def make_nets(dev):
@@ -621,6 +646,8 @@ def main():
     elapsed = time.perf_counter() - t0
     ops.KERNEL_TIMER = None
     assert bool(torch.isfinite(ret["rgb_map"]).all())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(ret, args.dump_outputs, args.rays)
 
     if use_dist:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)

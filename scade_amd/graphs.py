@@ -120,8 +120,11 @@ class GraphedTrainer:
         tr.bucket.end_backward()
         tr.reduce_grads()
         tr.finish(dev=True)
-        # the three loss terms of the step (:968-983) as static tensors too: the loop's log line reads them
-        self.terms = (aux["img_loss"], aux["carve"], aux["img_loss0"])
+        # the three loss terms of the step (:968-983) as static tensors too: the loop's log line reads them.
+        # Detached: kept with their grad_fn (the unfused loss, is_joint) they hold the warm-up step's autograd graph -
+        # and the scale / shift leaves' AccumulateGrad nodes, bound to the warm-up's side stream - alive into the
+        # capture, whose backward then accumulates on that uncaptured stream (host segfault in the replay)
+        self.terms = tuple(None if t is None else t.detach() for t in (aux["img_loss"], aux["carve"], aux["img_loss0"]))
         return aux["loss_report"]
 
     def _state(self):
