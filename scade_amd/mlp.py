@@ -6,14 +6,27 @@ import torch
 from . import ops
 
 
-
-def _check_train_precision(net):
-    if net.train_precision not in net.TRAIN_PRECISIONS:
+def _forward(net, train, inp, viewdirs, bb):
+    """-> (out, saved rows or None): the kernel and the weight blob of ``net``'s forward on x [P,60] (``viewdirs``
+    None) or pts [N,S,3]; ``train``: in its training precision, saving the rows its backward reads."""
+    if not train:
+        if viewdirs is None:
+            return ops.mlp_fwd_embedded(net.packed(), inp), None
+        return ops.mlp_fwd_points(net.packed(), inp, viewdirs, bb), None
+    tf = ops.TRAIN_FORMATS.get(net.train_precision)
+    if tf is None:
         raise ValueError("NeRF.train_precision must be one of %s" % (net.TRAIN_PRECISIONS,))
-
-
-def _needs_grad(params) -> bool:
-    return torch.is_grad_enabled() and any(p.requires_grad for p in params)
+    P = inp.shape[0] if viewdirs is None else inp.shape[0] * inp.shape[1]
+    if tf.code is not None:
+        acts = ops.mlp_acts_lp_alloc(P, inp.device)
+        return ops.mlp_fwd_lp(net.packed_lp(tf.bf16), tf.code, inp, viewdirs, bb, acts), acts
+    acts = ops.mlp_acts_alloc(P, inp.device)
+    if tf.step == "f16x3":
+        rows24 = net.train_precision == "f16x3"
+        return ops.mlp_fwd_f16(net.packed_f16(), inp, viewdirs, bb, acts, rows24=rows24), acts
+    if viewdirs is None:
+        return ops.mlp_fwd_embedded(net.packed(), inp, acts), acts
+    return ops.mlp_fwd_points(net.packed(), inp, viewdirs, bb, acts), acts
 
 
 class MlpEmbeddedFn(torch.autograd.Function):
@@ -21,18 +34,7 @@ class MlpEmbeddedFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, net, train, x, *params):
-        acts = None
-        lp = train and net.train_precision in ops.LP_FORMATS
-        if train:
-            _check_train_precision(net)
-            acts = (ops.mlp_acts_lp_alloc if lp else ops.mlp_acts_alloc)(x.shape[0], x.device)
-        if lp:
-            code, bf16 = ops.LP_FORMATS[net.train_precision]
-            out = ops.mlp_fwd_lp(net.packed_lp(bf16), code, x, None, None, acts)
-        elif train and net.train_precision in ("f16x3", "f16x3-dgrad"):
-            out = ops.mlp_fwd_f16(net.packed_f16(), x, None, None, acts, rows24=net.train_precision == "f16x3")
-        else:
-            out = ops.mlp_fwd_embedded(net.packed(), x, acts)
+        out, acts = _forward(net, train, x, None, None)
         ctx.net, ctx.mode = net, 0
         ctx.save_for_backward(x, acts if acts is not None else x.new_empty(0))
         return out
@@ -50,19 +52,7 @@ class MlpPointsFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, net, train, pts, viewdirs, bb, *params):
-        acts = None
-        lp = train and net.train_precision in ops.LP_FORMATS
-        if train:
-            _check_train_precision(net)
-            P = pts.shape[0] * pts.shape[1]
-            acts = (ops.mlp_acts_lp_alloc if lp else ops.mlp_acts_alloc)(P, pts.device)
-        if lp:
-            code, bf16 = ops.LP_FORMATS[net.train_precision]
-            out = ops.mlp_fwd_lp(net.packed_lp(bf16), code, pts, viewdirs, bb, acts)
-        elif train and net.train_precision in ("f16x3", "f16x3-dgrad"):
-            out = ops.mlp_fwd_f16(net.packed_f16(), pts, viewdirs, bb, acts, rows24=net.train_precision == "f16x3")
-        else:
-            out = ops.mlp_fwd_points(net.packed(), pts, viewdirs, bb, acts)
+        out, acts = _forward(net, train, pts, viewdirs, bb)
         ctx.net, ctx.mode, ctx.n_params = net, 1, len(params)
         ctx.save_for_backward(pts, viewdirs, bb, acts if acts is not None else pts.new_empty(0))
         return out

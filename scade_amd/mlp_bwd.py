@@ -80,13 +80,13 @@ def flush_deferred(items, after_net=None, defer=False):
             if after_net is not None:
                 after_net(n1)
             return (desc, (n0, n1)) if desc is not None else None
-        code, bf16 = ops.LP_FORMATS[prec]
+        tf = ops.TRAIN_FORMATS[prec]
         P0, P1 = g0.numel() // 4, g1.numel() // 4
         if ops.lp_point_tiles(P0) == ops.lp_point_tiles(P1):
             gm = [ops.GMAX_READY.pop(g.data_ptr(), None) for g in (g0, g1)]
             gmax = gm if (hook is None and all(t is not None for t in gm)) else None
-            desc = ops.mlp_bwd_lp2([n0.packed_t_lp(bf16), n1.packed_t_lp(bf16)], code, [a0, a1], [g0, g1], sinks,
-                                   after_first=hook, defer=defer and hook is None, gmax=gmax)
+            desc = ops.mlp_bwd_lp2([n0.packed_t_lp(tf.bf16), n1.packed_t_lp(tf.bf16)], tf.code, [a0, a1], [g0, g1],
+                                   sinks, after_first=hook, defer=defer and hook is None, gmax=gmax)
             if after_net is not None:
                 after_net(n1)
             return (desc, (n0, n1)) if desc is not None else None
@@ -98,15 +98,15 @@ def flush_deferred(items, after_net=None, defer=False):
 
 
 def _backward_now(net, acts, g_out, out):
-    if net.train_precision in ("f16x3", "f16x3-dgrad"):
+    tf = ops.TRAIN_FORMATS.get(net.train_precision)
+    if tf is None:
+        raise ValueError("NeRF.train_precision must be one of %s" % (net.TRAIN_PRECISIONS,))
+    if tf.step == "f16x3":
         return ops.mlp_bwd_f16(net.packed(), net.packed_t_f16(), acts, g_out,
                                wgrad_f16=net.train_precision == "f16x3", out=out)
-    if net.train_precision in ops.LP_FORMATS:
-        code, bf16 = ops.LP_FORMATS[net.train_precision]
-        return ops.mlp_bwd_lp(None, net.packed_t_lp(bf16), code, acts, g_out, out=out)
-    if net.train_precision == "f32":
-        return ops.mlp_bwd(net.packed(), net.packed_t(), acts, g_out, out=out)
-    raise ValueError("NeRF.train_precision must be one of %s" % (net.TRAIN_PRECISIONS,))
+    if tf.code is not None:
+        return ops.mlp_bwd_lp(None, net.packed_t_lp(tf.bf16), tf.code, acts, g_out, out=out)
+    return ops.mlp_bwd(net.packed(), net.packed_t(), acts, g_out, out=out)
 
 
 def mlp_backward(net, acts, g_out):

@@ -6,6 +6,7 @@ tensors, allocates outputs with torch and records what the backward kernels need
 from __future__ import annotations
 
 import ctypes
+from collections import namedtuple
 from typing import Optional, Sequence, Tuple
 
 import torch
@@ -78,9 +79,6 @@ class KernelTimer:
 KERNEL_TIMER: Optional[KernelTimer] = None
 PARAM_EPOCH = 0   # bumped by optimizers that update parameters through raw pointers
 N_PARAM_FLOATS = 589700
-# 16-bit training formats: name -> (format code of the scade_mlp_*_lp entries, weight packs are bf16?)
-#   "bf16-s8": bf16 arithmetic, the rows saved for the weight gradient (activations, dZ) stored as 8-bit e5m2
-LP_FORMATS = {"f16": (0, False), "bf16": (1, True), "bf16-s8": (2, True)}
 MLP_FLOP_PER_POINT = 2 * 587264      # algorithmic, unpadded
 
 
@@ -106,54 +104,97 @@ def _rows(t: Tensor, what: str) -> Tuple[Tensor, int]:
 # MLP
 # ---------------------------------------------------------------------------
 
-def mlp_packed_floats() -> int:
-    return int(_lib.load().scade_mlp_packed_floats())
+# The six weight-blob layouts the MLP kernels read: C pack entry (params[24], blob[, bf16 flag], stream), C size query
+# (elements of ``dtype`` per blob), dtype, and whether the entry takes the bf16 flag (then part of what a blob is for)
+PackLayout = namedtuple("PackLayout", "entry size dtype flag")
+PACK_LAYOUTS = {
+    "f32": PackLayout("scade_mlp_pack", "scade_mlp_packed_floats", torch.float32, False),          # exact forward
+    "f32_t": PackLayout("scade_mlp_pack_t", "scade_mlp_packed_t_floats", torch.float32, False),    # exact transposed
+    "f16x3": PackLayout("scade_mlp_pack_f16", "scade_mlp_packed_f16_bytes", torch.uint8, False),   # two-plane forward
+    "f16x3_t": PackLayout("scade_mlp_pack_t_f16", "scade_mlp_packed_t_f16_bytes", torch.uint8, False),  # transposed
+    "lp": PackLayout("scade_mlp_pack_lp", "scade_mlp_packed_lp_bytes", torch.uint8, True),         # 16-bit forward
+    "lp_t": PackLayout("scade_mlp_pack_t_lp", "scade_mlp_packed_t_lp_bytes", torch.uint8, True),   # 16-bit transposed
+}
 
 
-def mlp_pack(params: Sequence[Tensor], out: Optional[Tensor] = None) -> Tensor:
-    """params: the 24 tensors in PARAM_ORDER (device, fp32, contiguous)."""
+def layout_key(layout: str, key: tuple, bf16) -> tuple:
+    """What a blob of ``layout`` packed from the parameter state ``key`` (NeRF.pack_key) is valid for."""
+    return (bool(bf16),) + key if PACK_LAYOUTS[layout].flag else key
+
+
+def layout_blob(layout: str, cur: Optional[Tensor], dev) -> Tensor:
+    """``cur`` when it can hold a blob of ``layout`` on ``dev`` (to be re-packed in place), else a fresh tensor."""
+    spec = PACK_LAYOUTS[layout]
+    n = int(getattr(_lib.load(), spec.size)())
+    if cur is not None and cur.device == dev and cur.numel() == n and cur.dtype == spec.dtype:
+        return cur
+    return torch.empty(n, device=dev, dtype=spec.dtype)
+
+
+def _pack_layout(layout: str, params: Sequence[Tensor], out: Optional[Tensor] = None, bf16=None) -> Tensor:
+    """Pack the 24 parameters (PARAM_ORDER, fp32 device tensors) into a blob of ``layout``: ``out``, or a new tensor."""
+    spec = PACK_LAYOUTS[layout]
     if len(params) != 24:
-        raise ValueError("mlp_pack: expected 24 parameter tensors")
+        raise ValueError(f"{spec.entry}: expected 24 parameter tensors")
     keep = []
     for name, p in zip(PARAM_ORDER, params):
-        check(p, f"mlp_pack[{name}]")
+        check(p, f"{spec.entry}[{name}]")
         if tuple(p.shape) != PARAM_SHAPES[name]:
-            raise ValueError(f"mlp_pack[{name}]: shape {tuple(p.shape)} != {PARAM_SHAPES[name]} "
+            raise ValueError(f"{spec.entry}[{name}]: shape {tuple(p.shape)} != {PARAM_SHAPES[name]} "
                              "(only NeRF(D=8,W=256,input_ch=57,input_ch_views=3,skips=[4],"
                              "use_viewdirs=True) is implemented)")
         keep.append(_c(p.detach()))
     if out is None:
-        out = torch.empty(mlp_packed_floats(), device=keep[0].device, dtype=torch.float32)
+        out = layout_blob(layout, None, keep[0].device)
+    elif layout_blob(layout, out, keep[0].device) is not out:
+        raise ValueError(f"{spec.entry}: out is not a {layout} blob on {keep[0].device}")
     arr = (ctypes.c_void_p * 24)(*[t.data_ptr() for t in keep])
-    call("scade_mlp_pack", ctypes.cast(arr, ctypes.c_void_p), ptr(out), stream())
+    call(spec.entry, ctypes.cast(arr, ctypes.c_void_p), ptr(out), *((int(bf16),) if spec.flag else ()), stream())
     return out
 
 
-def mlp_pack_t(params: Sequence[Tensor], out: Optional[Tensor] = None) -> Tensor:
-    """Transposed weight pack for the dgrad chain (scade_mlp_pack_t)."""
-    keep = [_c(check(p, "mlp_pack_t").detach()) for p in params]
-    if out is None:
-        out = torch.empty(int(_lib.load().scade_mlp_packed_t_floats()), device=keep[0].device,
-                          dtype=torch.float32)
-    arr = (ctypes.c_void_p * 24)(*[t.data_ptr() for t in keep])
-    call("scade_mlp_pack_t", ctypes.cast(arr, ctypes.c_void_p), ptr(out), stream())
-    return out
+# the stand-alone pack of each layout
+def mlp_pack(params, out=None): return _pack_layout("f32", params, out)
+def mlp_pack_t(params, out=None): return _pack_layout("f32_t", params, out)
+def mlp_pack_f16(params, out=None): return _pack_layout("f16x3", params, out)
+def mlp_pack_t_f16(params, out=None): return _pack_layout("f16x3_t", params, out)
+def mlp_pack_lp(params, bf16, out=None): return _pack_layout("lp", params, out, bf16)
+def mlp_pack_t_lp(params, bf16, out=None): return _pack_layout("lp_t", params, out, bf16)
+
+
+# The training formats (NeRF.train_precision): the mlp_pack_step / StepPacks format that brings their blobs up to date
+# and its code in scade_mlp_pack_step / the opening launch's pack; the layouts the format owns as the opening launch's
+# (exact forward, 16-bit forward, transposed) slots - without the empty ones, the pack-step entry's arguments; the
+# scade_mlp_*_lp format code and bf16 flag of the 16-bit formats.  "f16x3-dgrad": the exact weight gradient on the f16x3
+# blobs; "bf16-s8": "bf16" with the rows saved for the weight gradient stored as 8-bit e5m2.
+TrainFormat = namedtuple("TrainFormat", "step step_code slots code bf16")
+_F32, _F16X3, _LP = ("f32", None, "f32_t"), ("f32", "f16x3", "f16x3_t"), (None, "lp", "lp_t")
+TRAIN_FORMATS = {
+    "f32": TrainFormat("f32", 0, _F32, None, None),
+    "f16x3": TrainFormat("f16x3", 3, _F16X3, None, None),
+    "f16x3-dgrad": TrainFormat("f16x3", 3, _F16X3, None, None),
+    "f16": TrainFormat("f16", 2, _LP, 0, False),
+    "bf16": TrainFormat("bf16", 1, _LP, 1, True),
+    "bf16-s8": TrainFormat("bf16", 1, _LP, 2, True),
+}
+# 16-bit training formats: name -> (format code of the scade_mlp_*_lp entries, weight packs are bf16?)
+LP_FORMATS = {p: (f.code, f.bf16) for p, f in TRAIN_FORMATS.items() if f.code is not None}
 
 
 def mlp_pack_step(nets, fmt: str) -> None:
-    """Bring the training weight packs of one or two NeRFs up to date with ONE launch (scade_mlp_pack_step): the
-    forward and the transposed layout of each network whose cached blobs are stale.  ``fmt``: "f32" (the exact
-    kernels' packs), "bf16" or "f16" (the 16-bit kernels' packs).  The blobs land in the networks' own caches
-    (NeRF.packed / packed_t / packed_lp / packed_t_lp return them without packing again)."""
-    lib = _lib.load()
-    code = {"f32": 0, "bf16": 1, "f16": 2}[fmt]
-    plist, fwd, tr, adopt = [], [], [], []
+    """Bring the training weight packs of one or two NeRFs up to date with ONE launch: the layouts of ``fmt``
+    (TRAIN_FORMATS: "f32", "bf16", "f16" -> scade_mlp_pack_step; "f16x3" -> scade_mlp_pack_step_f16x3) of each network
+    whose cached blobs are stale.  The blobs land in the networks' own caches (NeRF.pack returns them without packing
+    again)."""
+    tf = TRAIN_FORMATS[fmt]
+    layouts = [l for l in tf.slots if l is not None]
+    plist, cols, adopt = [], [[] for _ in layouts], []
     for net in nets:
         ps = net.ordered_params()
-        dev = ps[0].device
-        key = net.pack_key()
-        need_f, need_t = net.pack_stale(fmt, False, key), net.pack_stale(fmt, True, key)
-        if not (need_f or need_t):
+        key = net.pack_key(ps)
+        keys = [layout_key(l, key, tf.bf16) for l in layouts]
+        need = [net.stale(l, k) for l, k in zip(layouts, keys)]
+        if not any(need):
             continue
         # the 24 device pointers are part of ``key``; the tensor checks run once per set of pointers (they
         # cost 30 us per network and step otherwise), the parameters themselves keep the storage alive
@@ -167,58 +208,29 @@ def mlp_pack_step(nets, fmt: str) -> None:
             raise ValueError("mlp_pack_step: parameters must be contiguous")
         # a network's blobs are allocated once per format and re-packed IN PLACE ever after: their addresses are
         # baked into captured steps (graphs.py), and step_finish() packs into them at the end of every step
-        bf, bt = _train_blobs(net, fmt, dev, need_f, need_t)
+        dev = ps[0].device
+        blobs = [layout_blob(l, net._packs.get(l, (None,))[0], dev) if n else None for l, n in zip(layouts, need)]
         plist += ptrs
-        fwd.append(bf)
-        tr.append(bt)
-        adopt.append((net, bf, bt, key))
+        for col, b in zip(cols, blobs):
+            col.append(b)
+        adopt.append((net, blobs, keys))
     if not adopt:
         return
     vp = lambda ts: ctypes.cast((ctypes.c_void_p * len(ts))(*[None if t is None else t.data_ptr() for t in ts]),
                                 ctypes.c_void_p)
-    call("scade_mlp_pack_step", len(adopt), ctypes.cast((ctypes.c_void_p * len(plist))(*plist), ctypes.c_void_p), code,
-         vp(fwd), vp(tr), stream())
-    for net, bf, bt, key in adopt:
-        net.adopt_packs(fmt, bf, bt, key)
-
-
-def _blob(cur, numel, dtype, dev):
-    if cur is not None and cur.device == dev and cur.numel() == numel and cur.dtype == dtype:
-        return cur
-    return torch.empty(numel, device=dev, dtype=dtype)
-
-
-def _train_blobs(net, fmt, dev, need_f=True, need_t=True):
-    """(forward blob, transposed blob) of format "f32" | "bf16" | "f16" for ``net``: its existing tensors (to be
-    re-packed in place) or fresh ones."""
-    lib = _lib.load()
-    d = net.__dict__
-    if fmt == "f32":
-        bf = _blob(d.get("_packed"), int(lib.scade_mlp_packed_floats()), torch.float32, dev) if need_f else None
-        bt = _blob(d.get("_packed_t"), int(lib.scade_mlp_packed_t_floats()), torch.float32, dev) if need_t else None
+    n, pp = len(adopt), ctypes.cast((ctypes.c_void_p * len(plist))(*plist), ctypes.c_void_p)
+    if tf.step == "f16x3":
+        call("scade_mlp_pack_step_f16x3", n, pp, *map(vp, cols), stream())
     else:
-        bf = _blob(d.get("_packed_lp"), int(lib.scade_mlp_packed_lp_bytes()), torch.uint8, dev) if need_f else None
-        bt = _blob(d.get("_packed_t_lp"), int(lib.scade_mlp_packed_t_lp_bytes()), torch.uint8, dev) if need_t else None
-    return bf, bt
+        call("scade_mlp_pack_step", n, pp, tf.step_code, *map(vp, cols), stream())
+    for net, blobs, keys in adopt:
+        for l, b, k in zip(layouts, blobs, keys):
+            if b is not None:
+                net.adopt(l, b, k)
 
 
-def _train_blobs_f16x3(net, dev, need=(True, True, True)):
-    lib = _lib.load()
-    d = net.__dict__
-    be = _blob(d.get("_packed"), int(lib.scade_mlp_packed_floats()), torch.float32, dev) if need[0] else None
-    bf = _blob(d.get("_packed_f16"), int(lib.scade_mlp_packed_f16_bytes()), torch.uint8, dev) if need[1] else None
-    bt = _blob(d.get("_packed_t_f16"), int(lib.scade_mlp_packed_t_f16_bytes()), torch.uint8, dev) if need[2] else None
-    return be, bf, bt
-
-
-def _adopt_f16x3(net, be, bf, bt, key):
-    d = net.__dict__
-    if be is not None:
-        d["_packed"], d["_packed_key"] = be, key
-    if bf is not None:
-        d["_packed_f16"], d["_packed_f16_key"] = bf, key
-    if bt is not None:
-        d["_packed_t_f16"], d["_packed_t_f16_key"] = bt, key
+def mlp_pack_step_f16x3(nets) -> None:
+    mlp_pack_step(nets, "f16x3")
 
 
 # loss-scale maxima a step's loss launch produced for the output gradients it wrote: {g_out.data_ptr(): float32[256]
@@ -271,45 +283,6 @@ def step_finish(opt_a, opt_b, n_nets: int, lr_a=None, dev: bool = False, reduce:
     PARAM_EPOCH += 1
 
 
-def mlp_pack_step_f16x3(nets) -> None:
-    """The same for the split-precision training kernels (scade_mlp_pack_step_f16x3): per network the exact forward
-    blob (the dgrad's heads read the fp32 head weights), the two-plane forward blob and the two-plane transposed blob
-    - six stand-alone launches per step otherwise.  The blobs land in NeRF.packed / packed_f16 / packed_t_f16's caches."""
-    lib = _lib.load()
-    plist, ex, fw, tr, adopt = [], [], [], [], []
-    for net in nets:
-        ps = net.ordered_params()
-        dev = ps[0].device
-        key = net.pack_key()
-        d = net.__dict__
-        stale = lambda blob, k: blob is None or k != key or blob.device != dev
-        need = (stale(d.get("_packed"), d.get("_packed_key")), stale(d.get("_packed_f16"), d.get("_packed_f16_key")),
-                stale(d.get("_packed_t_f16"), d.get("_packed_t_f16_key")))
-        if not any(need):
-            continue
-        ptrs = tuple(k[0] for k in key[1:])
-        if d.get("_pack_checked") != ptrs:
-            for p in ps:
-                check(p, "mlp_pack_step_f16x3")
-            d["_pack_checked"] = ptrs
-        if not all(p.is_contiguous() for p in ps):
-            raise ValueError("mlp_pack_step_f16x3: parameters must be contiguous")
-        be, bf, bt = _train_blobs_f16x3(net, dev, need)
-        plist += ptrs
-        ex.append(be)
-        fw.append(bf)
-        tr.append(bt)
-        adopt.append((net, be, bf, bt, key))
-    if not adopt:
-        return
-    vp = lambda ts: ctypes.cast((ctypes.c_void_p * len(ts))(*[None if t is None else t.data_ptr() for t in ts]),
-                                ctypes.c_void_p)
-    call("scade_mlp_pack_step_f16x3", len(adopt), ctypes.cast((ctypes.c_void_p * len(plist))(*plist), ctypes.c_void_p),
-         vp(ex), vp(fw), vp(tr), stream())
-    for net, be, bf, bt, key in adopt:
-        _adopt_f16x3(net, be, bf, bt, key)
-
-
 def mlp_acts_alloc(P: int, device) -> Tensor:
     return torch.empty(int(_lib.load().scade_mlp_acts_floats(P)), device=device, dtype=torch.float32)
 
@@ -336,25 +309,6 @@ def mlp_bwd(packed: Tensor, packed_t: Tensor, acts: Tensor, g_out: Tensor, out: 
     if t0 is not None:
         KERNEL_TIMER.stop("mlp_bwd", t0, float(P) * 2 * MLP_FLOP_PER_POINT)
     return grad
-
-
-def mlp_pack_f16(params: Sequence[Tensor], out: Optional[Tensor] = None) -> Tensor:
-    """Two-plane fp16 weight pack for the split-precision inference kernel."""
-    keep = [_c(check(p, "mlp_pack_f16").detach()) for p in params]
-    if out is None:
-        out = torch.empty(int(_lib.load().scade_mlp_packed_f16_bytes()), device=keep[0].device,
-                          dtype=torch.uint8)
-    arr = (ctypes.c_void_p * 24)(*[t.data_ptr() for t in keep])
-    call("scade_mlp_pack_f16", ctypes.cast(arr, ctypes.c_void_p), ptr(out), stream())
-    return out
-
-
-def mlp_pack_t_f16(params: Sequence[Tensor]) -> Tensor:
-    keep = [_c(check(p, "mlp_pack_t_f16").detach()) for p in params]
-    out = torch.empty(int(_lib.load().scade_mlp_packed_t_f16_bytes()), device=keep[0].device, dtype=torch.uint8)
-    arr = (ctypes.c_void_p * 24)(*[t.data_ptr() for t in keep])
-    call("scade_mlp_pack_t_f16", ctypes.cast(arr, ctypes.c_void_p), ptr(out), stream())
-    return out
 
 
 def mlp_bwd_f16(packed: Tensor, packed_t_f16: Tensor, acts: Tensor, g_out: Tensor,
@@ -430,36 +384,20 @@ def mlp_fwd_f16(packed_f16: Tensor, inp: Tensor, viewdirs: Optional[Tensor], bb:
     return out
 
 
-def mlp_pack_lp(params: Sequence[Tensor], bf16: bool) -> Tensor:
-    """Single-plane 16-bit weight pack (fp16, or bf16 when ``bf16``) for scade_mlp_fwd_lp."""
-    keep = [_c(check(p, "mlp_pack_lp").detach()) for p in params]
-    out = torch.empty(int(_lib.load().scade_mlp_packed_lp_bytes()), device=keep[0].device, dtype=torch.uint8)
-    arr = (ctypes.c_void_p * 24)(*[t.data_ptr() for t in keep])
-    call("scade_mlp_pack_lp", ctypes.cast(arr, ctypes.c_void_p), ptr(out), int(bf16), stream())
-    return out
-
-
 def mlp_acts_lp_alloc(P: int, device) -> Tensor:
     return torch.empty(int(_lib.load().scade_mlp_acts_lp_bytes(P)), device=device, dtype=torch.uint8)
 
 
-def mlp_pack_t_lp(params: Sequence[Tensor], bf16: bool) -> Tensor:
-    keep = [_c(check(p, "mlp_pack_t_lp").detach()) for p in params]
-    out = torch.empty(int(_lib.load().scade_mlp_packed_t_lp_bytes()), device=keep[0].device, dtype=torch.uint8)
-    arr = (ctypes.c_void_p * 24)(*[t.data_ptr() for t in keep])
-    call("scade_mlp_pack_t_lp", ctypes.cast(arr, ctypes.c_void_p), ptr(out), int(bf16), stream())
-    return out
-
-
-def mlp_bwd_lp(packed: Optional[Tensor], packed_t_lp: Tensor, bf16: bool, acts: Tensor, g_out: Tensor,
+def mlp_bwd_lp(packed: Optional[Tensor], packed_t_lp: Tensor, code: int, acts: Tensor, g_out: Tensor,
                out: Optional[Tensor] = None) -> Tensor:
-    """16-bit dgrad + wgrad (fp32 accumulate, power-of-two loss scaling) -> flat gradient [589700]."""
+    """16-bit dgrad + wgrad (fp32 accumulate, power-of-two loss scaling) -> flat gradient [589700].  ``code``: the
+    format code of LP_FORMATS (0 = f16, 1 = bf16, 2 = bf16-s8)."""
     g = _c(check(g_out, "mlp_bwd_lp: g_out")).reshape(-1, 4)
     P = g.shape[0]
     ws = torch.empty(int(_lib.load().scade_mlp_bwd_lp_workspace_bytes(P)), device=g.device, dtype=torch.uint8)
     grad = _grad_out(out, g.device)
     t0 = KERNEL_TIMER.start() if KERNEL_TIMER is not None else None
-    call("scade_mlp_bwd_lp", ptr(packed), ptr(packed_t_lp), int(bf16), ptr(acts), ptr(g), P, ptr(ws), ptr(grad),
+    call("scade_mlp_bwd_lp", ptr(packed), ptr(packed_t_lp), int(code), ptr(acts), ptr(g), P, ptr(ws), ptr(grad),
          stream())
     if t0 is not None:
         KERNEL_TIMER.stop("mlp_bwd", t0, float(P) * 2 * MLP_FLOP_PER_POINT)
@@ -505,8 +443,9 @@ def mlp_bwd2(packed, packed_t, acts, g_out, outs, after_first=None, defer: bool 
     return desc
 
 
-def mlp_bwd_lp2(packed_t_lp, bf16: bool, acts, g_out, outs, after_first=None, defer: bool = False, gmax=None):
-    """16-bit backward of two network calls in one launch each (scade_mlp_bwd_lp2); see mlp_bwd2.  ``gmax``: per entry
+def mlp_bwd_lp2(packed_t_lp, code: int, acts, g_out, outs, after_first=None, defer: bool = False, gmax=None):
+    """16-bit backward of two network calls in one launch each (scade_mlp_bwd_lp2); see mlp_bwd2.  ``code``: the
+    format code of LP_FORMATS (0 = f16, 1 = bf16, 2 = bf16-s8).  ``gmax``: per entry
     the 256 loss-scale maxima the step's loss launch already produced (``GMAX_READY``), or None."""
     g = [_c(check(t, "mlp_bwd_lp2: g_out")).reshape(-1, 4) for t in g_out]
     P = [t.shape[0] for t in g]
@@ -516,7 +455,7 @@ def mlp_bwd_lp2(packed_t_lp, bf16: bool, acts, g_out, outs, after_first=None, de
     grads = [_grad_out(o, g[0].device) for o in outs]
     Pa = (ctypes.c_int * 2)(*P)
     t0 = KERNEL_TIMER.start() if KERNEL_TIMER is not None else None
-    args = (_host_ptrs(packed_t_lp), int(bf16), _host_ptrs(acts), _host_ptrs(g),
+    args = (_host_ptrs(packed_t_lp), int(code), _host_ptrs(acts), _host_ptrs(g),
             ctypes.cast(Pa, ctypes.c_void_p), _host_ptrs(ws), _host_ptrs(grads))
     desc = None
     if defer or gmax is not None:
@@ -566,28 +505,23 @@ class StepPacks:
 
     def __init__(self, nets, fmt: str):
         self.nets, self.fmt = list(nets), fmt
-        self.code = {"f32": 0, "bf16": 1, "f16": 2, "f16x3": 3}[fmt]
+        self.tf = TRAIN_FORMATS[fmt]
 
     def prepare(self):
-        (mlp_pack_step_f16x3 if self.fmt == "f16x3" else (lambda nets: mlp_pack_step(nets, self.fmt)))(self.nets)
+        mlp_pack_step(self.nets, self.fmt)
 
     def tail_args(self):
-        plist, ex, fw, tr = [], [], [], []
+        plist, cols = [], [[], [], []]
         for net in self.nets:
-            d = net.__dict__
             plist += [p.data_ptr() for p in net.ordered_params()]
-            if self.code == 3:
-                be, bf, bt = d.get("_packed"), d.get("_packed_f16"), d.get("_packed_t_f16")
-            elif self.code == 0:
-                be, bf, bt = d.get("_packed"), None, d.get("_packed_t")
-            else:
-                be, bf, bt = None, d.get("_packed_lp"), d.get("_packed_t_lp")
-            if (be is None and bf is None) or bt is None:
-                raise RuntimeError("StepPacks: the networks' training blobs do not exist yet (prepare() first)")
-            ex.append(be); fw.append(bf); tr.append(bt)
+            for col, l in zip(cols, self.tf.slots):
+                blob = None if l is None else net._packs.get(l, (None,))[0]
+                if l is not None and blob is None:
+                    raise RuntimeError("StepPacks: the networks' training blobs do not exist yet (prepare() first)")
+                col.append(blob)
         P = ctypes.c_void_p
         vp = lambda ts: ctypes.cast((P * len(ts))(*[None if t is None else t.data_ptr() for t in ts]), P)
-        return (self.code, len(self.nets), ctypes.cast((P * len(plist))(*plist), P), vp(ex), vp(fw), vp(tr))
+        return (self.tf.step_code, len(self.nets), ctypes.cast((P * len(plist))(*plist), P), *map(vp, cols))
 
 
 _NO_PACK = (-1, 0, None, None, None, None)
@@ -647,9 +581,10 @@ def lp_point_tiles(P: int) -> int:
     return int(_lib.load().scade_mlp_lp_point_tiles(int(P)))
 
 
-def mlp_fwd_lp(packed_lp: Tensor, bf16: bool, inp: Tensor, viewdirs: Optional[Tensor],
+def mlp_fwd_lp(packed_lp: Tensor, code: int, inp: Tensor, viewdirs: Optional[Tensor],
                bb: Optional[Tensor], acts: Optional[Tensor] = None) -> Tensor:
-    """16-bit-operand forward: inp [P,60] (viewdirs None) or pts [N,S,3] + viewdirs [N,3] + bb [4]."""
+    """16-bit-operand forward: inp [P,60] (viewdirs None) or pts [N,S,3] + viewdirs [N,3] + bb [4].  ``code``: the
+    format code of LP_FORMATS (0 = f16, 1 = bf16, 2 = bf16-s8; the blob must be bf16 for codes 1 and 2)."""
     check(inp, "mlp_fwd_lp: input")
     inp = _c(inp)
     if viewdirs is None:
@@ -657,7 +592,7 @@ def mlp_fwd_lp(packed_lp: Tensor, bf16: bool, inp: Tensor, viewdirs: Optional[Te
             raise ValueError("mlp_fwd_lp: x must be [P,60]")
         P = inp.shape[0]
         out = torch.empty(P, 4, device=inp.device, dtype=torch.float32)
-        call("scade_mlp_fwd_lp", ptr(packed_lp), int(bf16), 0, ptr(inp), None, 0, None, P, 1, ptr(out), ptr(acts),
+        call("scade_mlp_fwd_lp", ptr(packed_lp), int(code), 0, ptr(inp), None, 0, None, P, 1, ptr(out), ptr(acts),
              stream())
         return out
     N, S = inp.shape[0], inp.shape[1]
@@ -665,7 +600,7 @@ def mlp_fwd_lp(packed_lp: Tensor, bf16: bool, inp: Tensor, viewdirs: Optional[Te
     bb = _c(check(bb, "mlp_fwd_lp: bb"))
     out = torch.empty(N, S, 4, device=inp.device, dtype=torch.float32)
     t0 = KERNEL_TIMER.start() if KERNEL_TIMER is not None else None
-    call("scade_mlp_fwd_lp", ptr(packed_lp), int(bf16), 1, ptr(inp), ptr(viewdirs), vstride, ptr(bb), N * S, S,
+    call("scade_mlp_fwd_lp", ptr(packed_lp), int(code), 1, ptr(inp), ptr(viewdirs), vstride, ptr(bb), N * S, S,
          ptr(out), ptr(acts), stream())
     if t0 is not None:
         KERNEL_TIMER.stop("mlp_fwd_lp_kernel", t0, float(N * S) * MLP_FLOP_PER_POINT)

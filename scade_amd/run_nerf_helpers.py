@@ -143,8 +143,8 @@ class NeRF(nn.Module):
             self.rgb_linear = DenseLayer(W // 2, 3, activation="linear")
         else:
             self.output_linear = DenseLayer(W, output_ch, activation="linear")
-        self._packed = None
-        self._packed_key = None
+        # the weight blobs the kernels read: {ops.PACK_LAYOUTS name: (blob, what it was packed for)} (see pack())
+        self._packs = {}
         # "f32": exact fp32 MFMA everywhere.  "f16x3": no-grad forwards use the split-precision
         # kernel (two fp16 planes per value, three f16 MFMAs per product; ~1e-6 relative error).
         # "f16" / "bf16": single-plane 16-bit operands, fp32 accumulate (ordinary mixed precision,
@@ -188,95 +188,49 @@ class NeRF(nn.Module):
         self.__dict__["_ordered_cache"] = c
         return c[2]
 
-    def packed(self):
-        """MFMA-ordered parameter blob, rebuilt whenever a parameter changed in place."""
+    # -- weight blobs (ops.PACK_LAYOUTS) --------------------------------------------------------------------
+    def pack_key(self, ps=None):
+        """The parameter state a blob is packed from: pointers, in-place versions and ops.PARAM_EPOCH."""
+        return (ops.PARAM_EPOCH,) + tuple((p.data_ptr(), p._version) for p in (ps or self.ordered_params()))
+
+    def stale(self, layout, key):
+        """Is the cached blob of ``layout`` missing, on another device, or packed for another ``key``
+        (ops.layout_key of pack_key())?"""
+        cur = self._packs.get(layout)
+        return cur is None or cur[1] != key or cur[0].device != self.ordered_params()[0].device
+
+    def adopt(self, layout, blob, key):
+        """Take over a blob of ``layout`` packed for ``key`` (ops.mlp_pack_step writes the blobs itself).  (One dict
+        in the instance dict: nn.Module.__setattr__ costs 3 us per assignment.)"""
+        self._packs[layout] = (blob, key)
+
+    def pack(self, layout, bf16=None):
+        """The blob of ``layout``, re-packed when a parameter changed in place or was re-homed, or the bf16 flag or
+        the device changed.  A stale blob is re-packed IN PLACE when it fits: graph-captured steps hold its address."""
+        ps = self.ordered_params()
+        key = ops.layout_key(layout, self.pack_key(ps), bf16)
+        cur = self._packs.get(layout)
+        if cur is not None and cur[1] == key and cur[0].device == ps[0].device:
+            return cur[0]
         self._require_supported()
-        ps = self.ordered_params()
-        key = (ops.PARAM_EPOCH,) + tuple((p.data_ptr(), p._version) for p in ps)
-        if self._packed is None or key != self._packed_key or self._packed.device != ps[0].device:
-            self._packed = ops.mlp_pack(ps, None if self._packed is None or
-                                        self._packed.device != ps[0].device else self._packed)
-            self._packed_key = key
-        return self._packed
+        blob = ops.layout_blob(layout, None if cur is None else cur[0], ps[0].device)
+        self._packs[layout] = (ops._pack_layout(layout, ps, blob, bf16), key)
+        return blob
 
-    def packed_t(self):
-        """Transposed weight pack for the backward, same invalidation rule as packed()."""
-        ps = self.ordered_params()
-        key = (ops.PARAM_EPOCH,) + tuple((p.data_ptr(), p._version) for p in ps)
-        if getattr(self, "_packed_t", None) is None or key != self._packed_t_key \
-                or self._packed_t.device != ps[0].device:
-            self._packed_t = ops.mlp_pack_t(ps)
-            self._packed_t_key = key
-        return self._packed_t
+    def packed(self): return self.pack("f32")
+    def packed_t(self): return self.pack("f32_t")
+    def packed_f16(self): return self.pack("f16x3")
+    def packed_t_f16(self): return self.pack("f16x3_t")
+    def packed_lp(self, bf16): return self.pack("lp", bf16)
+    def packed_t_lp(self, bf16): return self.pack("lp_t", bf16)
 
-    def packed_f16(self):
-        ps = self.ordered_params()
-        key = (ops.PARAM_EPOCH,) + tuple((p.data_ptr(), p._version) for p in ps)
-        if getattr(self, "_packed_f16", None) is None or key != self._packed_f16_key \
-                or self._packed_f16.device != ps[0].device:
-            self._packed_f16 = ops.mlp_pack_f16(ps)
-            self._packed_f16_key = key
-        return self._packed_f16
-
-    def packed_t_f16(self):
-        ps = self.ordered_params()
-        key = (ops.PARAM_EPOCH,) + tuple((p.data_ptr(), p._version) for p in ps)
-        if getattr(self, "_packed_t_f16", None) is None or key != self._packed_t_f16_key \
-                or self._packed_t_f16.device != ps[0].device:
-            self._packed_t_f16 = ops.mlp_pack_t_f16(ps)
-            self._packed_t_f16_key = key
-        return self._packed_t_f16
-
-    def packed_lp(self, bf16):
-        """Single-plane fp16 / bf16 weight pack of the 16-bit inference kernel (same invalidation rule)."""
-        ps = self.ordered_params()
-        key = (bool(bf16), ops.PARAM_EPOCH) + tuple((p.data_ptr(), p._version) for p in ps)
-        if getattr(self, "_packed_lp", None) is None or key != self._packed_lp_key \
-                or self._packed_lp.device != ps[0].device:
-            self._packed_lp = ops.mlp_pack_lp(ps, bf16)
-            self._packed_lp_key = key
-        return self._packed_lp
-
-    def packed_t_lp(self, bf16):
-        ps = self.ordered_params()
-        key = (bool(bf16), ops.PARAM_EPOCH) + tuple((p.data_ptr(), p._version) for p in ps)
-        if getattr(self, "_packed_t_lp", None) is None or key != self._packed_t_lp_key \
-                or self._packed_t_lp.device != ps[0].device:
-            self._packed_t_lp = ops.mlp_pack_t_lp(ps, bf16)
-            self._packed_t_lp_key = key
-        return self._packed_t_lp
-
-    # -- the Trainer's one-launch pack of both networks (ops.mlp_pack_step) ------------------------------
-    def pack_key(self):
-        return (ops.PARAM_EPOCH,) + tuple((p.data_ptr(), p._version) for p in self.ordered_params())
-
-    def pack_stale(self, fmt, transposed, key=None):
-        """Is the cached training pack of this format stale? (fmt: "f32" | "bf16" | "f16")"""
-        key = self.pack_key() if key is None else key
-        dev = self.ordered_params()[0].device
-        if fmt == "f32":
-            blob, k = (getattr(self, "_packed_t", None), getattr(self, "_packed_t_key", None)) if transposed \
-                else (self._packed, self._packed_key)
-            return blob is None or k != key or blob.device != dev
-        blob, k = (getattr(self, "_packed_t_lp", None), getattr(self, "_packed_t_lp_key", None)) if transposed \
-            else (getattr(self, "_packed_lp", None), getattr(self, "_packed_lp_key", None))
-        return blob is None or k != (fmt == "bf16",) + key or blob.device != dev
-
-    def adopt_packs(self, fmt, fwd, transposed, key):
-        """Take over blobs ops.mlp_pack_step wrote for the parameter state ``key`` describes.  (Plain attributes,
-        written through the instance dict: nn.Module.__setattr__ costs 3 us per assignment.)"""
-        d = self.__dict__
-        if fmt == "f32":
-            if fwd is not None:
-                d["_packed"], d["_packed_key"] = fwd, key
-            if transposed is not None:
-                d["_packed_t"], d["_packed_t_key"] = transposed, key
-        else:
-            k = (fmt == "bf16",) + key
-            if fwd is not None:
-                d["_packed_lp"], d["_packed_lp_key"] = fwd, k
-            if transposed is not None:
-                d["_packed_t_lp"], d["_packed_t_lp_key"] = transposed, k
+    # the cached blobs under their earlier attribute names (read-only; None before the first pack)
+    _packed = property(lambda self: self._packs.get("f32", (None,))[0])
+    _packed_t = property(lambda self: self._packs.get("f32_t", (None,))[0])
+    _packed_f16 = property(lambda self: self._packs.get("f16x3", (None,))[0])
+    _packed_t_f16 = property(lambda self: self._packs.get("f16x3_t", (None,))[0])
+    _packed_lp = property(lambda self: self._packs.get("lp", (None,))[0])
+    _packed_t_lp = property(lambda self: self._packs.get("lp_t", (None,))[0])
 
     def warm_packs(self):
         """Bring the weight pack of the current inference precision up to date on the CURRENT stream
@@ -299,8 +253,8 @@ class NeRF(nn.Module):
     def _fast_forward(self, inp, viewdirs, bb):
         if self.inference_precision == "f16x3":
             return ops.mlp_fwd_f16(self.packed_f16(), inp, viewdirs, bb)
-        bf16 = self.inference_precision == "bf16"
-        return ops.mlp_fwd_lp(self.packed_lp(bf16), bf16, inp, viewdirs, bb)
+        code, bf16 = ops.LP_FORMATS[self.inference_precision]
+        return ops.mlp_fwd_lp(self.packed_lp(bf16), code, inp, viewdirs, bb)
 
     def forward(self, x):
         """x [P, 60] = [gamma(pts) | viewdir] -> [P,4] (helpers:223-247)."""
