@@ -94,13 +94,22 @@ __device__ __forceinline__ unsigned long long layer_store(const f32x16 (&acc)[NT
 }
 
 #ifdef FWD_TRACE
-__device__ unsigned long long fwd_trace[4 * 4 * 24];   // [inference wg 0/1, training wg 0/1][wave][layer 1..4][6 stamps]
-__device__ unsigned long long fwd_sect[4 * 16];        // [kernel x wg]: wave 0's stamps at the section boundaries
-#define FS_STAMP(I) if (PT == 2 && (blockIdx.x == 1300 || blockIdx.x == 1301) && threadIdx.x == 0) \
-    fwd_sect[((SAVE ? 2 : 0) + (blockIdx.x - 1300)) * 16 + (I)] = clock64();
+// -DFWD_TRACE (a variant build: SCADE_AB_FLAGS, scade_amd/build.py; tools/probe_fwd_trace.py): core-clock stamps of EVERY
+// workgroup of the inference kernel at every section boundary, one row of FT_N stamps per wave, per launch-size class
+// (the 1,024-workgroup coarse launch / the 3,072-workgroup fine launch), plus each wave's HW_ID / XCC_ID (which CU and
+// SIMD it ran on: the analysis pairs the two workgroups that shared a CU)
+constexpr int FT_N = 64, FT_WG = 3072;
+__device__ unsigned long long fwd_trace[2 * FT_WG * 4 * FT_N];
+__device__ unsigned fwd_hwid[2 * FT_WG * 4 * 2];
+#define FT_ON (PT == 2 && !SAVE && MODE == 1 && blockIdx.x < FT_WG && lane == 0)
+#define FT_ROW (((gridDim.x > 1024 ? 1 : 0) * FT_WG + blockIdx.x) * 4 + wave)
+#define FT_AT(I) if (FT_ON) fwd_trace[FT_ROW * FT_N + (I)] = clock64();
 #else
-#define FS_STAMP(I)
+#define FT_AT(I)
 #endif
+// stamp slots: 0 kernel start, 1 prologue done, 2 + 6 * l + {0 k-loop start, 1 k-loop end, 2 barrier 1 passed,
+// 3 epilogue done, 4 tile copy issued, 5 barrier 2 passed} for MFMA layer l (0..7, 8 feature, 9 views), 62 end
+#define FT_STAMP(L, I) FT_AT(2 + 6 * (L) + (I))
 template <int MODE, bool SAVE, int PT>
 __global__ __launch_bounds__(256, 2) void mlp_fwd_kernel(MlpFwdArgs a) {
   constexpr int TM = tile_pts(PT);     // points of this workgroup (shadows the 64-point default)
@@ -114,7 +123,7 @@ __global__ __launch_bounds__(256, 2) void mlp_fwd_kernel(MlpFwdArgs a) {
   const int P = a.P;
   const float* __restrict__ pk = a.packed;
 
-  FS_STAMP(0)
+  FT_AT(0)
   // ---------------- prologue: embedding tile [64][60] (+ zeroed tail pad) ----
   if (tid < 4) ebuf[TM * EMB_STRIDE + tid] = 0.f;
   if (MODE == 0) {
@@ -165,6 +174,7 @@ __global__ __launch_bounds__(256, 2) void mlp_fwd_kernel(MlpFwdArgs a) {
     }
   }
   __syncthreads();
+  FT_AT(1)
   if (SAVE) {   // emb rows [64]: gamma(57) | 0 0 0 | view(3) | 0   (coalesced 256-B rows, 16-byte chunks)
     float* eo = a.acts + acts_emb_off(P);
     for (int i = tid; i < TM * 16; i += 256) {
@@ -193,16 +203,6 @@ __global__ __launch_bounds__(256, 2) void mlp_fwd_kernel(MlpFwdArgs a) {
 #define WBASE(L) (reinterpret_cast<const f32x4*>(pk + off_w(L)) + \
                   ((L) == L_VIEWS ? wave : nt0) * kb_total(L) * 64)
 
-  // -DFWD_TRACE (a variant build: SCADE_AB_FLAGS, scade_amd/build.py; tools/probe_fwd_trace.py): core-clock stamps of
-  // two workgroups of the launch's third round at the phase boundaries of layers 1..4 -
-  // {k-loop start, k-loop end, barrier passed, epilogue done, tile copy issued, second barrier passed}
-#ifdef FWD_TRACE
-#define FT_STAMP(L, I)                                                                                      \
-  if (PT == 2 && (L) >= 1 && (L) <= 4 && (blockIdx.x == 1300 || blockIdx.x == 1301) && lane == 0)              \
-    fwd_trace[(((SAVE ? 2 : 0) + (blockIdx.x - 1300)) * 4 + wave) * 24 + ((L) - 1) * 6 + (I)] = clock64();
-#else
-#define FT_STAMP(L, I)
-#endif
 #define PTS_LAYER(L, LNEXT, KBP, PRE)                                                              \
   {                                                                                                \
     FT_STAMP(L, 0)                                                                                 \
@@ -223,22 +223,15 @@ __global__ __launch_bounds__(256, 2) void mlp_fwd_kernel(MlpFwdArgs a) {
     FT_STAMP(L, 5)                                                                                 \
   }
 
-  FS_STAMP(1)
   an[0] = WBASE(0)[lane];
   an[1] = WBASE(0)[kb_total(0) * 64 + lane];
   load_bias<2>(bias, pk + off_b(0), nt0, lane);
   PTS_LAYER(0, 1, 8, ebuf)
-  FS_STAMP(2)
   PTS_LAYER(1, 2, 0, ebuf)
-  FS_STAMP(3)
   PTS_LAYER(2, 3, 0, ebuf)
-  FS_STAMP(4)
   PTS_LAYER(3, 4, 0, ebuf)
-  FS_STAMP(5)
   PTS_LAYER(4, 5, 0, ebuf)
-  FS_STAMP(6)
   PTS_LAYER(5, 6, 8, ebuf)
-  FS_STAMP(7)
 
   // embedding tile is dead now: reuse its head as the view pad [64][8]
   {
@@ -254,9 +247,7 @@ __global__ __launch_bounds__(256, 2) void mlp_fwd_kernel(MlpFwdArgs a) {
   // (visibility of the view pad is covered by the barriers of layers 6/7)
 
   PTS_LAYER(6, 7, 0, ebuf)
-  FS_STAMP(8)
   PTS_LAYER(7, L_FEAT, 0, ebuf)
-  FS_STAMP(9)
 #undef PTS_LAYER
 
   // ---------------- alpha head: 256 -> 1 on the VALU -------------------------
@@ -281,30 +272,39 @@ __global__ __launch_bounds__(256, 2) void mlp_fwd_kernel(MlpFwdArgs a) {
     if (SAVE && sub == 0 && head_store && p0 + row < P) a.acts[acts_alpha_off(P) + p0 + row] = alpha;
   }
 
-  FS_STAMP(10)
   // ---------------- feature_linear: 256 -> 256, no activation ----------------
+  FT_STAMP(8, 0)
   layer_gemm<2, 0, 32, EMB_STRIDE, PT>(acc, an, WBASE(L_FEAT), WBASE(L_VIEWS), 0, ebuf, hbuf, lane, bias);
   f32x4 biasv[1][4];
   load_bias<1>(biasv, pk + off_b(L_VIEWS), wave, lane);
+  FT_STAMP(8, 1)
   __syncthreads();
+  FT_STAMP(8, 2)
   layer_store<2, false, PT>(acc, nt0, hbuf, lane);
+  FT_STAMP(8, 3)
   if (SAVE) save_tile_wave<64, PT>(hbuf, a.acts + acts_slot_off(P, SLOT_FEAT), p0, P, 64 * wave, lane);
+  FT_STAMP(8, 4)
   __syncthreads();
+  FT_STAMP(8, 5)
 
-  FS_STAMP(11)
   // ---------------- views_linears[0]: [view pad | feature] -> 128, ReLU ------
   {
     f32x16 accv[1][PT];
     // (an[1] is unused by the one-tile views layer; the trailing prefetch re-reads block 0)
+    FT_STAMP(9, 0)
     layer_gemm<1, 1, 32, VIEW_PAD, PT>(accv, an, WBASE(L_VIEWS), WBASE(L_VIEWS), 0, ebuf, hbuf, lane, biasv);
+    FT_STAMP(9, 1)
     __syncthreads();
+      FT_STAMP(9, 2)
     layer_store<1, true, PT>(accv, wave, hbuf, lane);
+    FT_STAMP(9, 3)
     if (SAVE) save_tile_wave<32, PT>(hbuf, a.acts + acts_slot_off(P, SLOT_VIEWS_H), p0, P, 32 * wave, lane);
+    FT_STAMP(9, 4)
     __syncthreads();
+      FT_STAMP(9, 5)
   }
 
 #undef WBASE
-  FS_STAMP(12)
   // ---------------- rgb head 128 -> 3, softplus(alpha, beta=10) --------------
   {
     const int row = PT == 2 ? tid >> 2 : (tid >> 2) & 31, sub = tid & 3;
@@ -335,7 +335,13 @@ __global__ __launch_bounds__(256, 2) void mlp_fwd_kernel(MlpFwdArgs a) {
       *reinterpret_cast<f32x4*>(a.out + (size_t)(p0 + row) * 4) = o;
     }
   }
-  FS_STAMP(13)
+  FT_AT(62)
+#ifdef FWD_TRACE
+  if (FT_ON) {
+    fwd_hwid[FT_ROW * 2] = __builtin_amdgcn_s_getreg((31 << 11) | 4);      // HW_ID: wave, SIMD, CU, SH, SE
+    fwd_hwid[FT_ROW * 2 + 1] = __builtin_amdgcn_s_getreg((31 << 11) | 20); // XCC_ID
+  }
+#endif
 }
 
 // ---------------------------------------------------------------------------
@@ -355,9 +361,14 @@ __global__ void mlp_pack_kernel(PackArgs a) { pack_fwd_row(a.p, a.packed, blockI
 // ---------------------------------------------------------------------------
 using namespace scade;
 #ifdef FWD_TRACE
-extern "C" int scade_debug_fwd_trace(unsigned long long* out) {
-  if (hipMemcpyFromSymbol(out + 4 * 4 * 24, HIP_SYMBOL(scade::fwd_sect), sizeof(unsigned long long) * 4 * 16) != hipSuccess) return -1;
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(scade::fwd_trace), sizeof(unsigned long long) * 4 * 4 * 24);
+// out: [2 * FT_WG * 4 * FT_N] stamps; hwid: [2 * FT_WG * 4 * 2]
+extern "C" int scade_debug_fwd_trace(unsigned long long* out, unsigned* hwid) {
+  if (hipMemcpyFromSymbol(hwid, HIP_SYMBOL(scade::fwd_hwid), sizeof(unsigned) * 2 * FT_WG * 4 * 2) != hipSuccess) return -1;
+  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(scade::fwd_trace), sizeof(unsigned long long) * 2 * FT_WG * 4 * FT_N);
+}
+extern "C" int scade_debug_fwd_trace_clear(void) {
+  static unsigned long long z[2 * FT_WG * 4 * FT_N];
+  return (int)hipMemcpyToSymbol(HIP_SYMBOL(scade::fwd_trace), z, sizeof(z));
 }
 #endif
 

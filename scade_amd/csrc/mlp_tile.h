@@ -71,6 +71,22 @@ __device__ __forceinline__ void layer_gemm_b(f32x16 (&acc)[NT][PT], f32x4 (&an)[
           acc[t][p] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t][j], b[p][j], acc[t][p], 0, 0, 0);
   };
 
+  // the wave's weight fragments through a buffer descriptor of its weight block: voffset = the lane's 16 bytes (one
+  // register for the whole loop), the (n-tile, k-block) offset in an SGPR.  A flat pointer per fragment cost a 64-bit
+  // v_add_co / v_addc pair (plus the s_nop between them) on the fp32 lanes the MFMAs run on: 263 of the headline
+  // kernel's 1,944 VALU instructions, and 3 % of the render step (profiles/r07_fwd_idle_attribution.txt)
+  // (readfirstlane returns an int: each half goes through an unsigned, so the low word is not sign-extended into
+  // the high one)
+  const unsigned long long wa = reinterpret_cast<unsigned long long>(wp);
+  const unsigned wlo = __builtin_amdgcn_readfirstlane((unsigned)wa), whi = __builtin_amdgcn_readfirstlane((unsigned)(wa >> 32));
+  const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
+      reinterpret_cast<void*>(((unsigned long long)whi << 32) | wlo), 0, NT * KB * 1024, 0x00020000);
+  const int wvoff = lane * 16;
+  auto load_a = [&](int t, int kb) {
+    typedef unsigned u32x4_ __attribute__((ext_vector_type(4)));
+    const u32x4_ v = __builtin_amdgcn_raw_buffer_load_b128(wrs, wvoff, (t * KB + kb) * 1024, 0);
+    return __builtin_bit_cast(f32x4, v);
+  };
   f32x4 bn[2];
   load_b(0, bn[0], bn[1]);
 
@@ -81,7 +97,7 @@ __device__ __forceinline__ void layer_gemm_b(f32x16 (&acc)[NT][PT], f32x4 (&an)[
     b[0] = bn[0];
     if (PT > 1) b[1] = bn[1];
 #pragma unroll
-    for (int t = 0; t < NT; ++t) an[t] = wp[(t * KB + kb + 1) * 64 + lane];
+    for (int t = 0; t < NT; ++t) an[t] = load_a(t, kb + 1);
     load_b(kb + 1, bn[0], bn[1]);
     // keep the next block's loads ABOVE this block's MFMAs (hipcc otherwise sinks
     // them below the last use of a[]/b[] to reuse the registers: no prefetch)
