@@ -7,26 +7,13 @@ from . import ops
 
 
 def _forward(net, train, inp, viewdirs, bb):
-    """-> (out, saved rows or None): the kernel and the weight blob of ``net``'s forward on x [P,60] (``viewdirs``
-    None) or pts [N,S,3]; ``train``: in its training precision, saving the rows its backward reads."""
+    """-> (out, saved rows or None): ``net``'s forward on x [P,60] (``viewdirs`` None) or pts [N,S,3]; ``train``: in
+    its training precision, saving the rows its backward reads (else exact fp32)."""
     if not train:
-        if viewdirs is None:
-            return ops.mlp_fwd_embedded(net.packed(), inp), None
-        return ops.mlp_fwd_points(net.packed(), inp, viewdirs, bb), None
-    tf = ops.TRAIN_FORMATS.get(net.train_precision)
-    if tf is None:
-        raise ValueError("NeRF.train_precision must be one of %s" % (net.TRAIN_PRECISIONS,))
-    P = inp.shape[0] if viewdirs is None else inp.shape[0] * inp.shape[1]
-    if tf.code is not None:
-        acts = ops.mlp_acts_lp_alloc(P, inp.device)
-        return ops.mlp_fwd_lp(net.packed_lp(tf.bf16), tf.code, inp, viewdirs, bb, acts), acts
-    acts = ops.mlp_acts_alloc(P, inp.device)
-    if tf.step == "f16x3":
-        rows24 = net.train_precision == "f16x3"
-        return ops.mlp_fwd_f16(net.packed_f16(), inp, viewdirs, bb, acts, rows24=rows24), acts
-    if viewdirs is None:
-        return ops.mlp_fwd_embedded(net.packed(), inp, acts), acts
-    return ops.mlp_fwd_points(net.packed(), inp, viewdirs, bb, acts), acts
+        return ops.mlp_fwd_net(net, ops.TRAIN_FORMATS["f32"], inp, viewdirs, bb), None
+    tf = ops.train_format(net)
+    acts = ops.mlp_acts(tf, inp.numel() // inp.shape[-1], inp.device)
+    return ops.mlp_fwd_net(net, tf, inp, viewdirs, bb, acts), acts
 
 
 class MlpEmbeddedFn(torch.autograd.Function):

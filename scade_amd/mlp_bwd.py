@@ -46,47 +46,45 @@ class DeferredBackward:
         return False
 
 
-def _pair_key(net):
-    p = net.train_precision
-    return p if (p == "f32" or p == "f16x3" or p in ops.LP_FORMATS) else None
+def _pair_format(items):
+    """the TrainFormat of two queued backwards that one joint launch sequence can take (two networks of one format
+    whose family has pair entries for it), else None"""
+    if len(items) != 2 or items[0][0] is items[1][0] or items[0][0].train_precision != items[1][0].train_precision:
+        return None
+    tf = ops.TRAIN_FORMATS.get(items[0][0].train_precision)
+    # (the joint f16x3 entries read the 24-bit rows only)
+    return None if tf is None or tf.rows24 is False else tf
 
 
 def flush_deferred(items, after_net=None, defer=False):
     """-> (ops.ReduceDesc, (net of entry 0, net of entry 1)) when ``defer`` and the joint launch took it, else None"""
-    if len(items) == 2 and _pair_key(items[0][0]) is not None and _pair_key(items[0][0]) == _pair_key(items[1][0]) \
-            and items[0][0] is not items[1][0]:
+    # the maxima the step's loss launch left are for this flush alone: a later backward may reuse the addresses
+    ready = {}
+    if ops.GMAX_READY:
+        ready = dict(ops.GMAX_READY)
+        ops.GMAX_READY.clear()
+    tf = _pair_format(items)
+    if tf is not None:
+        fam = ops.MLP_FAMILIES[tf.family]
         if after_net is not None:
             items = sorted(items, key=lambda it: it[2].numel())          # the shorter backward first
+        elif tf.family == "f16x3":
+            # (the larger call first: its workgroups are the launch's body, the smaller one's fill the tail)
+            items = sorted(items, key=lambda it: -it[2].numel())
         (n0, a0, g0), (n1, a1, g1) = items
-        prec = n0.train_precision
-        if prec == "f16x3":
-            if after_net is None:
-                # (the larger call first: its workgroups are the launch's body, the smaller one's fill the tail)
-                (n0, a0, g0), (n1, a1, g1) = sorted(items, key=lambda it: -it[2].numel())
-                desc = ops.mlp_bwd_f16_2([n0.packed(), n1.packed()], [n0.packed_t_f16(), n1.packed_t_f16()], [a0, a1],
-                                         [g0, g1], [n0._grad_sink, n1._grad_sink], defer=defer)
-                return (desc, (n0, n1)) if desc is not None else None
-            # (a staged gradient exchange wants the first network's gradient early: one launch sequence per network,
-            # the shorter backward first - ``items`` was sorted above)
-            for net, acts, g in items:
-                _backward_now(net, acts, g, net._grad_sink)
-                after_net(net)
-            return
-        sinks = [n0._grad_sink, n1._grad_sink]
-        hook = None if after_net is None else (lambda: after_net(n0))
-        if prec == "f32":
-            desc = ops.mlp_bwd2([n0.packed(), n1.packed()], [n0.packed_t(), n1.packed_t()], [a0, a1], [g0, g1], sinks,
-                                after_first=hook, defer=defer and hook is None)
-            if after_net is not None:
-                after_net(n1)
-            return (desc, (n0, n1)) if desc is not None else None
-        tf = ops.TRAIN_FORMATS[prec]
-        P0, P1 = g0.numel() // 4, g1.numel() // 4
-        if ops.lp_point_tiles(P0) == ops.lp_point_tiles(P1):
-            gm = [ops.GMAX_READY.pop(g.data_ptr(), None) for g in (g0, g1)]
-            gmax = gm if (hook is None and all(t is not None for t in gm)) else None
-            desc = ops.mlp_bwd_lp2([n0.packed_t_lp(tf.bf16), n1.packed_t_lp(tf.bf16)], tf.code, [a0, a1], [g0, g1],
-                                   sinks, after_first=hook, defer=defer and hook is None, gmax=gmax)
+        # (without a phases entry, a staged gradient exchange that wants the first network's gradient early gets one
+        # launch sequence per network)
+        joint = after_net is None or fam.bwd2_phases is not None
+        if joint and fam.tiles is not None:
+            q = getattr(ops._lib.load(), fam.tiles)
+            joint = q(g0.numel() // 4) == q(g1.numel() // 4)
+        if joint:
+            hook = None if after_net is None else (lambda: after_net(n0))
+            gmax = [ready.get(g0.data_ptr()), ready.get(g1.data_ptr())] if fam.gmax and hook is None else None
+            if gmax is not None and (gmax[0] is None or gmax[1] is None):
+                gmax = None
+            desc = ops.mlp_bwd_nets(tf, (n0, n1), [a0, a1], [g0, g1], [n0._grad_sink, n1._grad_sink], after_first=hook,
+                                    defer=defer and hook is None, gmax=gmax)
             if after_net is not None:
                 after_net(n1)
             return (desc, (n0, n1)) if desc is not None else None
@@ -98,15 +96,7 @@ def flush_deferred(items, after_net=None, defer=False):
 
 
 def _backward_now(net, acts, g_out, out):
-    tf = ops.TRAIN_FORMATS.get(net.train_precision)
-    if tf is None:
-        raise ValueError("NeRF.train_precision must be one of %s" % (net.TRAIN_PRECISIONS,))
-    if tf.step == "f16x3":
-        return ops.mlp_bwd_f16(net.packed(), net.packed_t_f16(), acts, g_out,
-                               wgrad_f16=net.train_precision == "f16x3", out=out)
-    if tf.code is not None:
-        return ops.mlp_bwd_lp(None, net.packed_t_lp(tf.bf16), tf.code, acts, g_out, out=out)
-    return ops.mlp_bwd(net.packed(), net.packed_t(), acts, g_out, out=out)
+    return ops.mlp_bwd_net(net, ops.train_format(net), acts, g_out, out)
 
 
 def mlp_backward(net, acts, g_out):

@@ -162,20 +162,47 @@ def mlp_pack_lp(params, bf16, out=None): return _pack_layout("lp", params, out, 
 def mlp_pack_t_lp(params, bf16, out=None): return _pack_layout("lp_t", params, out, bf16)
 
 
-# The training formats (NeRF.train_precision): the mlp_pack_step / StepPacks format that brings their blobs up to date
-# and its code in scade_mlp_pack_step / the opening launch's pack; the layouts the format owns as the opening launch's
-# (exact forward, 16-bit forward, transposed) slots - without the empty ones, the pack-step entry's arguments; the
-# scade_mlp_*_lp format code and bf16 flag of the 16-bit formats.  "f16x3-dgrad": the exact weight gradient on the f16x3
-# blobs; "bf16-s8": "bf16" with the rows saved for the weight gradient stored as 8-bit e5m2.
-TrainFormat = namedtuple("TrainFormat", "step step_code slots code bf16")
+# The three kernel families of the MLP: the forward entry; the size query of the rows a training forward saves (elements of
+# ``acts_dtype`` for P points); the backward entries of one network, of a pair, of a pair with a deferred reduce and of
+# a pair in two phases around a first-network hook (None: no such entry); the workspace size queries of a single and a
+# pair launch (None: each network's single one) in elements of ``ws_dtype``; the PACK_LAYOUTS the forward reads and the
+# two the backward reads (None: passed as NULL, left out of the pair entries); the forward's KERNEL_TIMER label; the
+# size query the two networks of a pair launch must agree on (or None); whether the deferred pair entry takes the
+# output gradients and precomputed loss-scale maxima; the function of this module a step's single-network backward
+# goes through (looked up when called: what replaces it sees the step's backward).
+MlpFamily = namedtuple("MlpFamily", "fwd acts acts_dtype bwd bwd2 bwd2_deferred bwd2_phases ws ws2 ws_dtype fwd_blob "
+                                    "bwd_blobs timer tiles gmax bwd_fn")
+_f32, _u8 = torch.float32, torch.uint8
+MLP_FAMILIES = {
+    "f32": MlpFamily("scade_mlp_fwd", "scade_mlp_acts_floats", _f32, "scade_mlp_bwd", "scade_mlp_bwd2",
+                     "scade_mlp_bwd2_deferred", "scade_mlp_bwd2_phases", "scade_mlp_bwd_workspace_floats",
+                     "scade_mlp_bwd2_workspace_floats", _f32, "f32", ("f32", "f32_t"), "mlp_fwd_kernel", None, False,
+                     "mlp_bwd"),
+    "f16x3": MlpFamily("scade_mlp_fwd_f16", "scade_mlp_acts_floats", _f32, "scade_mlp_bwd_f16", "scade_mlp_bwd_f16_2",
+                       "scade_mlp_bwd_f16_2_deferred", None, "scade_mlp_bwd_workspace_floats", None, _f32, "f16x3",
+                       ("f32", "f16x3_t"), "mlp_fwd_f16_kernel", None, False, "mlp_bwd_f16"),
+    "lp": MlpFamily("scade_mlp_fwd_lp", "scade_mlp_acts_lp_bytes", _u8, "scade_mlp_bwd_lp", "scade_mlp_bwd_lp2",
+                    "scade_mlp_bwd_lp2_deferred", "scade_mlp_bwd_lp2_phases", "scade_mlp_bwd_lp_workspace_bytes",
+                    "scade_mlp_bwd_lp2_workspace_bytes", _u8, "lp", (None, "lp_t"), "mlp_fwd_lp_kernel",
+                    "scade_mlp_lp_point_tiles", True, "mlp_bwd_lp"),
+}
+
+# The training formats (NeRF.train_precision; the inference precisions are rows of it too): the mlp_pack_step /
+# StepPacks format that brings their blobs up to date and its code in scade_mlp_pack_step / the opening launch's pack;
+# the layouts the format owns as the opening launch's (exact forward, 16-bit forward, transposed) slots - without the
+# empty ones, the pack-step entry's arguments; the scade_mlp_*_lp format code and bf16 flag of the 16-bit formats; the
+# MLP_FAMILIES kernels; for f16x3, whether the saved rows are the 24-bit ones its weight gradient reads.  "f16x3-dgrad":
+# the exact weight gradient on the f16x3 blobs; "bf16-s8": "bf16" with the rows saved for the weight gradient stored as
+# 8-bit e5m2.
+TrainFormat = namedtuple("TrainFormat", "step step_code slots code bf16 family rows24")
 _F32, _F16X3, _LP = ("f32", None, "f32_t"), ("f32", "f16x3", "f16x3_t"), (None, "lp", "lp_t")
 TRAIN_FORMATS = {
-    "f32": TrainFormat("f32", 0, _F32, None, None),
-    "f16x3": TrainFormat("f16x3", 3, _F16X3, None, None),
-    "f16x3-dgrad": TrainFormat("f16x3", 3, _F16X3, None, None),
-    "f16": TrainFormat("f16", 2, _LP, 0, False),
-    "bf16": TrainFormat("bf16", 1, _LP, 1, True),
-    "bf16-s8": TrainFormat("bf16", 1, _LP, 2, True),
+    "f32": TrainFormat("f32", 0, _F32, None, None, "f32", None),
+    "f16x3": TrainFormat("f16x3", 3, _F16X3, None, None, "f16x3", True),
+    "f16x3-dgrad": TrainFormat("f16x3", 3, _F16X3, None, None, "f16x3", False),
+    "f16": TrainFormat("f16", 2, _LP, 0, False, "lp", None),
+    "bf16": TrainFormat("bf16", 1, _LP, 1, True, "lp", None),
+    "bf16-s8": TrainFormat("bf16", 1, _LP, 2, True, "lp", None),
 }
 # 16-bit training formats: name -> (format code of the scade_mlp_*_lp entries, weight packs are bf16?)
 LP_FORMATS = {p: (f.code, f.bf16) for p, f in TRAIN_FORMATS.items() if f.code is not None}
@@ -234,7 +261,7 @@ def mlp_pack_step_f16x3(nets) -> None:
 
 
 # loss-scale maxima a step's loss launch produced for the output gradients it wrote: {g_out.data_ptr(): float32[256]
-# device tensor}, consumed (popped) by the joint 16-bit backward of the same step (mlp_bwd.flush_deferred)
+# device tensor}, for the joint 16-bit backward of the same step; mlp_bwd.flush_deferred empties it whatever it launches
 GMAX_READY = {}
 
 
@@ -283,8 +310,14 @@ def step_finish(opt_a, opt_b, n_nets: int, lr_a=None, dev: bool = False, reduce:
     PARAM_EPOCH += 1
 
 
-def mlp_acts_alloc(P: int, device) -> Tensor:
-    return torch.empty(int(_lib.load().scade_mlp_acts_floats(P)), device=device, dtype=torch.float32)
+def _opt(v) -> tuple:
+    """an optional int argument of a C entry: () when the entry does not take it (None)"""
+    return () if v is None else (int(v),)
+
+
+def _host_ptrs(ts):
+    """HOST array of device pointers (None -> NULL; the scade_*2 entries take two-entry host arrays)."""
+    return ctypes.cast((ctypes.c_void_p * len(ts))(*[None if t is None else t.data_ptr() for t in ts]), ctypes.c_void_p)
 
 
 def _grad_out(out: Optional[Tensor], device) -> Tensor:
@@ -297,185 +330,164 @@ def _grad_out(out: Optional[Tensor], device) -> Tensor:
     return out
 
 
-def mlp_bwd(packed: Tensor, packed_t: Tensor, acts: Tensor, g_out: Tensor, out: Optional[Tensor] = None) -> Tensor:
-    """-> flat gradient [589700] in PARAM_ORDER (written into ``out`` when given)."""
-    g = _c(check(g_out, "mlp_bwd: g_out")).reshape(-1, 4)
-    P = g.shape[0]
-    ws = torch.empty(int(_lib.load().scade_mlp_bwd_workspace_floats(P)), device=g.device,
-                     dtype=torch.float32)
-    grad = _grad_out(out, g.device)
-    t0 = KERNEL_TIMER.start() if KERNEL_TIMER is not None else None
-    call("scade_mlp_bwd", ptr(packed), ptr(packed_t), ptr(acts), ptr(g), P, ptr(ws), ptr(grad), stream())
-    if t0 is not None:
-        KERNEL_TIMER.stop("mlp_bwd", t0, float(P) * 2 * MLP_FLOP_PER_POINT)
-    return grad
+def _acts(fam: MlpFamily, P: int, device) -> Tensor:
+    return torch.empty(int(getattr(_lib.load(), fam.acts)(P)), device=device, dtype=fam.acts_dtype)
 
 
-def mlp_bwd_f16(packed: Tensor, packed_t_f16: Tensor, acts: Tensor, g_out: Tensor,
-                wgrad_f16: bool = True, out: Optional[Tensor] = None) -> Tensor:
-    """Split-precision dgrad + weight gradient -> flat gradient [589700] in PARAM_ORDER.  ``wgrad_f16``: the
-    split-precision weight gradient on 24-bit saved rows (the forward must have run with ``rows24=True``); False: the
-    exact fp32 weight gradient on fp32 rows."""
-    g = _c(check(g_out, "mlp_bwd_f16: g_out")).reshape(-1, 4)
-    P = g.shape[0]
-    ws = torch.empty(int(_lib.load().scade_mlp_bwd_workspace_floats(P)), device=g.device, dtype=torch.float32)
-    grad = _grad_out(out, g.device)
-    t0 = KERNEL_TIMER.start() if KERNEL_TIMER is not None else None
-    call("scade_mlp_bwd_f16", ptr(packed), ptr(packed_t_f16), ptr(acts), ptr(g), P, int(wgrad_f16), ptr(ws),
-         ptr(grad), stream())
-    if t0 is not None:
-        KERNEL_TIMER.stop("mlp_bwd", t0, float(P) * 2 * MLP_FLOP_PER_POINT)
-    return grad
-
-
-def mlp_bwd_f16_2(packed, packed_t_f16, acts, g_out, outs, defer: bool = False):
-    """Split-precision backward (24-bit saved rows) of TWO network calls - the coarse + fine NeRF of a train step - as
-    one zeroing launch, one dgrad launch, one weight-gradient launch and one reduce (scade_mlp_bwd_f16_2).  Every
-    argument: a pair; ``outs`` = the two flat gradient buffers [589700], OVERWRITTEN.  Same bits as two
-    ``mlp_bwd_f16`` calls (same tiles, same chunks, same summation order).  ``defer``: no reduce launch - the partial
-    rows stay in the workspaces and the returned ``ReduceDesc`` hands them to ``step_finish`` (``outs`` untouched)."""
-    g = [_c(check(t, "mlp_bwd_f16_2: g_out")).reshape(-1, 4) for t in g_out]
-    P = [t.shape[0] for t in g]
-    lib = _lib.load()
-    ws = [torch.empty(int(lib.scade_mlp_bwd_workspace_floats(P[i])), device=g[i].device, dtype=torch.float32)
-          for i in range(2)]
-    grads = [_grad_out(o, g[0].device) for o in outs]
-    Pa = (ctypes.c_int * 2)(*P)
-    t0 = KERNEL_TIMER.start() if KERNEL_TIMER is not None else None
-    desc = None
-    if defer:
-        desc = ReduceDesc(ws)
-        call("scade_mlp_bwd_f16_2_deferred", _host_ptrs(packed), _host_ptrs(packed_t_f16), _host_ptrs(acts), _host_ptrs(g),
-             ctypes.cast(Pa, ctypes.c_void_p), _host_ptrs(ws), ctypes.cast(desc.buf, ctypes.c_void_p), stream())
-    else:
-        call("scade_mlp_bwd_f16_2", _host_ptrs(packed), _host_ptrs(packed_t_f16), _host_ptrs(acts), _host_ptrs(g),
-             ctypes.cast(Pa, ctypes.c_void_p), 1, _host_ptrs(ws), _host_ptrs(grads), stream())
-    if t0 is not None:
-        KERNEL_TIMER.stop("mlp_bwd", t0, float(P[0] + P[1]) * 2 * MLP_FLOP_PER_POINT)
-    return desc
-
-
-def mlp_fwd_f16(packed_f16: Tensor, inp: Tensor, viewdirs: Optional[Tensor], bb: Optional[Tensor],
-                acts: Optional[Tensor] = None, rows24: bool = False) -> Tensor:
-    """Split-precision forward: inp [P,60] (viewdirs None) or pts [N,S,3] + viewdirs [N,3] + bb [4].  ``rows24``
-    (with ``acts``): the saved rows in the 24-bit form the split-precision weight gradient reads (mode + 2) - what
-    ``mlp_bwd_f16(wgrad_f16=True)`` expects; False: fp32 rows (``wgrad_f16=False``, the exact weight gradient)."""
-    check(inp, "mlp_fwd_f16: input")
-    inp = _c(inp)
-    if rows24 and acts is None:
-        raise ValueError("mlp_fwd_f16: rows24 needs the training workspace")
-    fmt = 2 if rows24 else 0
+def _fwd(fam: MlpFamily, blob: Tensor, inp: Tensor, viewdirs: Optional[Tensor], bb: Optional[Tensor],
+         acts: Optional[Tensor] = None, code=None, rows24: bool = False) -> Tensor:
+    """The forward of ``fam`` on x [P,60] (mode 0, ``viewdirs`` None) or pts [N,S,3] + viewdirs [N,3] + bb [4] (mode 1)
+    -> [P,4] / [N,S,4]; ``acts``: the rows saved for the backward (at least ``fam.acts`` of P).  ``code``: the
+    LP_FORMATS code of the 16-bit entry; ``rows24``: the f16x3 entry saves the 24-bit rows (mode + 2)."""
+    what = fam.fwd[len("scade_"):]
+    inp = _c(check(inp, f"{what}: input"))
     if viewdirs is None:
         if inp.dim() != 2 or inp.shape[1] != 60:
-            raise ValueError("mlp_fwd_f16: x must be [P,60]")
-        P = inp.shape[0]
-        out = torch.empty(P, 4, device=inp.device, dtype=torch.float32)
-        call("scade_mlp_fwd_f16", ptr(packed_f16), 0 + fmt, ptr(inp), None, 0, None, P, 1, ptr(out), ptr(acts), stream())
-        return out
-    N, S = inp.shape[0], inp.shape[1]
-    viewdirs, vstride = _rows(viewdirs, "mlp_fwd_f16: viewdirs")
-    bb = _c(check(bb, "mlp_fwd_f16: bb"))
-    out = torch.empty(N, S, 4, device=inp.device, dtype=torch.float32)
-    t0 = KERNEL_TIMER.start() if KERNEL_TIMER is not None else None
-    call("scade_mlp_fwd_f16", ptr(packed_f16), 1 + fmt, ptr(inp), ptr(viewdirs), vstride, ptr(bb), N * S, S,
+            raise ValueError(f"{what}: x must be [P,60], got {tuple(inp.shape)}")
+        P, S, vstride, mode = inp.shape[0], 1, 0, 0
+        shape = (P, 4)
+    else:
+        if inp.dim() != 3 or inp.shape[-1] != 3:
+            raise ValueError(f"{what}: pts must be [N,S,3], got {tuple(inp.shape)}")
+        N, S = inp.shape[0], inp.shape[1]
+        if check(viewdirs, f"{what}: viewdirs").shape != (N, 3):
+            raise ValueError(f"{what}: viewdirs must be [{N},3], got {tuple(viewdirs.shape)}")
+        if check(bb, f"{what}: bb").shape != (4,):
+            raise ValueError(f"{what}: bb must be [4], got {tuple(bb.shape)}")
+        viewdirs, vstride = _rows(viewdirs, f"{what}: viewdirs")
+        P, bb, mode = N * S, _c(bb), 1
+        shape = (N, S, 4)
+    if acts is not None:
+        need = int(getattr(_lib.load(), fam.acts)(P)) * fam.acts_dtype.itemsize
+        if acts.nbytes < need or not acts.is_contiguous():
+            raise ValueError(f"{what}: acts must be a contiguous buffer of at least {need} bytes for {P} points")
+    elif rows24:
+        raise ValueError(f"{what}: rows24 needs the training workspace")
+    out = torch.empty(shape, device=inp.device, dtype=torch.float32)
+    t0 = KERNEL_TIMER.start() if (KERNEL_TIMER is not None and mode) else None
+    call(fam.fwd, ptr(blob), *_opt(code), mode + 2 * bool(rows24), ptr(inp), ptr(viewdirs), vstride, ptr(bb), P, S,
          ptr(out), ptr(acts), stream())
     if t0 is not None:
-        KERNEL_TIMER.stop("mlp_fwd_f16_kernel", t0, float(N * S) * MLP_FLOP_PER_POINT)
+        KERNEL_TIMER.stop(fam.timer, t0, float(P) * MLP_FLOP_PER_POINT)
     return out
 
 
-def mlp_acts_lp_alloc(P: int, device) -> Tensor:
-    return torch.empty(int(_lib.load().scade_mlp_acts_lp_bytes(P)), device=device, dtype=torch.uint8)
-
-
-def mlp_bwd_lp(packed: Optional[Tensor], packed_t_lp: Tensor, code: int, acts: Tensor, g_out: Tensor,
-               out: Optional[Tensor] = None) -> Tensor:
-    """16-bit dgrad + wgrad (fp32 accumulate, power-of-two loss scaling) -> flat gradient [589700].  ``code``: the
-    format code of LP_FORMATS (0 = f16, 1 = bf16, 2 = bf16-s8)."""
-    g = _c(check(g_out, "mlp_bwd_lp: g_out")).reshape(-1, 4)
+def _bwd(fam: MlpFamily, packed: Optional[Tensor], packed_t: Tensor, acts: Tensor, g_out: Tensor,
+         out: Optional[Tensor] = None, code=None, wgrad_f16=None) -> Tensor:
+    """The backward of ``fam`` (dgrad chain + weight gradient + reduce) of one network call -> flat gradient [589700]
+    in PARAM_ORDER (written into ``out`` when given).  ``code``: as _fwd; ``wgrad_f16``: the f16x3 weight gradient
+    on 24-bit rows (False: the exact one on fp32 rows)."""
+    g = _c(check(g_out, f"{fam.bwd[len('scade_'):]}: g_out")).reshape(-1, 4)
     P = g.shape[0]
-    ws = torch.empty(int(_lib.load().scade_mlp_bwd_lp_workspace_bytes(P)), device=g.device, dtype=torch.uint8)
+    ws = torch.empty(int(getattr(_lib.load(), fam.ws)(P)), device=g.device, dtype=fam.ws_dtype)
     grad = _grad_out(out, g.device)
     t0 = KERNEL_TIMER.start() if KERNEL_TIMER is not None else None
-    call("scade_mlp_bwd_lp", ptr(packed), ptr(packed_t_lp), int(code), ptr(acts), ptr(g), P, ptr(ws), ptr(grad),
+    call(fam.bwd, ptr(packed), ptr(packed_t), *_opt(code), ptr(acts), ptr(g), P, *_opt(wgrad_f16), ptr(ws), ptr(grad),
          stream())
     if t0 is not None:
         KERNEL_TIMER.stop("mlp_bwd", t0, float(P) * 2 * MLP_FLOP_PER_POINT)
     return grad
 
 
-def _host_ptrs(ts):
-    """HOST array of device pointers (the scade_*2 entries take two-entry host arrays)."""
-    return ctypes.cast((ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts]), ctypes.c_void_p)
-
-
-def mlp_bwd2(packed, packed_t, acts, g_out, outs, after_first=None, defer: bool = False):
-    """Exact backward of TWO network calls (coarse + fine NeRF of a train step) as one dgrad launch, one
-    weight-gradient launch and one reduce (scade_mlp_bwd2).  Every argument: a pair; ``outs`` = the two flat
-    gradient buffers [589700], OVERWRITTEN.  ``after_first``: a callable run when the FIRST entry's gradient is
-    complete on the stream (scade_mlp_bwd2_phases: joint dgrad, entry 0's weight gradient + reduce, callback, entry
-    1's) - a sharded step starts entry 0's gradient exchange there, under entry 1's weight gradient.  ``defer``: no
-    reduce launch - the returned ``ReduceDesc`` hands the partial rows to ``step_finish`` (``outs`` untouched)."""
-    g = [_c(check(t, "mlp_bwd2: g_out")).reshape(-1, 4) for t in g_out]
+def _bwd_pair(fam: MlpFamily, packed, packed_t, acts, g_out, outs, code=None, wgrad_f16=None, after_first=None,
+              defer: bool = False, gmax=None) -> Optional[ReduceDesc]:
+    """The backward of ``fam`` of TWO network calls - the coarse + fine NeRF of a train step - as one joint launch
+    sequence: same bits as two _bwd calls.  Every argument: a pair (``packed``: ignored when ``fam`` reads no forward
+    blob); ``outs`` = the two flat gradient buffers [589700], OVERWRITTEN.  ``after_first``: a callable run when the
+    FIRST entry's gradient is complete on the stream (``fam.bwd2_phases``: joint dgrad, entry 0's weight gradient +
+    reduce, callback, entry 1's) - a sharded step starts entry 0's gradient exchange there.  ``defer``: no reduce
+    launch - the returned ``ReduceDesc`` hands the partial rows to ``step_finish`` (``outs`` untouched).  ``gmax``
+    (``fam.gmax``): per entry the 256 loss-scale maxima the step's loss launch already produced (GMAX_READY)."""
+    what = fam.bwd2[len("scade_"):]
+    if after_first is not None and (defer or gmax is not None):
+        raise ValueError(f"{what}: a deferred reduce / precomputed maxima have no first-network hook")
+    if after_first is not None and fam.bwd2_phases is None:
+        raise ValueError(f"{what}: has no first-network hook")
+    if gmax is not None and not fam.gmax:
+        raise ValueError(f"{what}: takes no precomputed maxima")
+    g = [_c(check(t, f"{what}: g_out")).reshape(-1, 4) for t in g_out]
     P = [t.shape[0] for t in g]
     lib = _lib.load()
-    ws = [torch.empty(int(lib.scade_mlp_bwd2_workspace_floats(P[i], P[1 - i])), device=g[i].device, dtype=torch.float32)
-          for i in range(2)]
+    # (without a pair query, each network's workspace is the one of its own launch)
+    ws = [torch.empty(int(getattr(lib, fam.ws2)(P[i], P[1 - i]) if fam.ws2 else getattr(lib, fam.ws)(P[i])),
+                      device=g[i].device, dtype=fam.ws_dtype) for i in range(2)]
     grads = [_grad_out(o, g[0].device) for o in outs]
-    Pa = (ctypes.c_int * 2)(*P)
+    blobs = [_host_ptrs(b) for l, b in zip(fam.bwd_blobs, (packed, packed_t)) if l is not None]
+    head = (*blobs, *_opt(code), _host_ptrs(acts), _host_ptrs(g), ctypes.cast((ctypes.c_int * 2)(*P), ctypes.c_void_p))
     t0 = KERNEL_TIMER.start() if KERNEL_TIMER is not None else None
-    args = (_host_ptrs(packed), _host_ptrs(packed_t), _host_ptrs(acts), _host_ptrs(g),
-            ctypes.cast(Pa, ctypes.c_void_p), _host_ptrs(ws), _host_ptrs(grads))
-    desc = None
-    if defer:
-        if after_first is not None:
-            raise ValueError("mlp_bwd2: a deferred reduce has no first-network hook")
-        desc = ReduceDesc(ws)
-        call("scade_mlp_bwd2_deferred", *args[:6], ctypes.cast(desc.buf, ctypes.c_void_p), stream())
-    elif after_first is None:
-        call("scade_mlp_bwd2", *args, stream())
-    else:
-        call("scade_mlp_bwd2_phases", *args, 3, stream())
-        after_first()
-        call("scade_mlp_bwd2_phases", *args, 4, stream())
-    if t0 is not None:
-        KERNEL_TIMER.stop("mlp_bwd", t0, float(P[0] + P[1]) * 2 * MLP_FLOP_PER_POINT)
-    return desc
-
-
-def mlp_bwd_lp2(packed_t_lp, code: int, acts, g_out, outs, after_first=None, defer: bool = False, gmax=None):
-    """16-bit backward of two network calls in one launch each (scade_mlp_bwd_lp2); see mlp_bwd2.  ``code``: the
-    format code of LP_FORMATS (0 = f16, 1 = bf16, 2 = bf16-s8).  ``gmax``: per entry
-    the 256 loss-scale maxima the step's loss launch already produced (``GMAX_READY``), or None."""
-    g = [_c(check(t, "mlp_bwd_lp2: g_out")).reshape(-1, 4) for t in g_out]
-    P = [t.shape[0] for t in g]
-    lib = _lib.load()
-    ws = [torch.empty(int(lib.scade_mlp_bwd_lp2_workspace_bytes(P[i], P[1 - i])), device=g[i].device, dtype=torch.uint8)
-          for i in range(2)]
-    grads = [_grad_out(o, g[0].device) for o in outs]
-    Pa = (ctypes.c_int * 2)(*P)
-    t0 = KERNEL_TIMER.start() if KERNEL_TIMER is not None else None
-    args = (_host_ptrs(packed_t_lp), int(code), _host_ptrs(acts), _host_ptrs(g),
-            ctypes.cast(Pa, ctypes.c_void_p), _host_ptrs(ws), _host_ptrs(grads))
     desc = None
     if defer or gmax is not None:
-        if after_first is not None:
-            raise ValueError("mlp_bwd_lp2: a deferred reduce / precomputed maxima have no first-network hook")
         desc = ReduceDesc(ws) if defer else None
-        gm = None if gmax is None else ctypes.cast((ctypes.c_void_p * 2)(*[None if t is None else t.data_ptr() for t in gmax]),
-                                                   ctypes.c_void_p)
-        call("scade_mlp_bwd_lp2_deferred", *args, gm, None if desc is None else ctypes.cast(desc.buf, ctypes.c_void_p),
-             stream())
+        tail = (_host_ptrs(grads), None if gmax is None else _host_ptrs(gmax)) if fam.gmax else ()
+        call(fam.bwd2_deferred, *head, _host_ptrs(ws), *tail,
+             None if desc is None else ctypes.cast(desc.buf, ctypes.c_void_p), stream())
     elif after_first is None:
-        call("scade_mlp_bwd_lp2", *args, stream())
+        call(fam.bwd2, *head, *_opt(wgrad_f16), _host_ptrs(ws), _host_ptrs(grads), stream())
     else:
-        call("scade_mlp_bwd_lp2_phases", *args, 3, stream())
+        args = (*head, _host_ptrs(ws), _host_ptrs(grads))
+        call(fam.bwd2_phases, *args, 3, stream())
         after_first()
-        call("scade_mlp_bwd_lp2_phases", *args, 4, stream())
+        call(fam.bwd2_phases, *args, 4, stream())
     if t0 is not None:
         KERNEL_TIMER.stop("mlp_bwd", t0, float(P[0] + P[1]) * 2 * MLP_FLOP_PER_POINT)
     return desc
 
+
+# a NeRF in one of its formats (TRAIN_FORMATS; the inference precisions are rows of it too): the blobs of the format's
+# family from the network's cache and the arguments from the row
+def train_format(net) -> TrainFormat:
+    tf = TRAIN_FORMATS.get(net.train_precision)
+    if tf is None:
+        raise ValueError("NeRF.train_precision must be one of %s" % (tuple(TRAIN_FORMATS),))
+    return tf
+
+
+def mlp_acts(tf: TrainFormat, P: int, device) -> Tensor:
+    """the saved-rows buffer of a training forward of P points in ``tf``"""
+    return _acts(MLP_FAMILIES[tf.family], P, device)
+
+
+def mlp_fwd_net(net, tf: TrainFormat, inp, viewdirs, bb, acts=None) -> Tensor:
+    fam = MLP_FAMILIES[tf.family]
+    # (an inference forward saves no rows, so no 24-bit ones either)
+    return _fwd(fam, net.pack(fam.fwd_blob, tf.bf16), inp, viewdirs, bb, acts, tf.code, acts is not None and tf.rows24)
+
+
+def mlp_bwd_net(net, tf: TrainFormat, acts, g_out, out=None) -> Tensor:
+    fam = MLP_FAMILIES[tf.family]
+    blobs = [None if l is None else net.pack(l, tf.bf16) for l in fam.bwd_blobs]
+    extra = {k: v for k, v in (("code", tf.code), ("wgrad_f16", tf.rows24)) if v is not None}
+    return globals()[fam.bwd_fn](*blobs, acts=acts, g_out=g_out, out=out, **extra)
+
+
+def mlp_bwd_nets(tf: TrainFormat, nets, acts, g_out, outs, **kw) -> Optional[ReduceDesc]:
+    """_bwd_pair of two networks in ``tf`` (``kw``: after_first, defer, gmax)"""
+    fam = MLP_FAMILIES[tf.family]
+    n0, n1 = nets
+    blobs = [None if l is None else [n0.pack(l, tf.bf16), n1.pack(l, tf.bf16)] for l in fam.bwd_blobs]
+    return _bwd_pair(fam, *blobs, acts, g_out, outs, tf.code, tf.rows24, **kw)
+
+
+# the entries under their earlier names (tests and tools call them with blobs of their own)
+F32, F16X3, LP = MLP_FAMILIES["f32"], MLP_FAMILIES["f16x3"], MLP_FAMILIES["lp"]
+def mlp_acts_alloc(P, device): return _acts(F32, P, device)
+def mlp_acts_lp_alloc(P, device): return _acts(LP, P, device)
+def mlp_fwd_embedded(packed, x, acts=None): return _fwd(F32, packed, x, None, None, acts)
+def mlp_fwd_points(packed, pts, viewdirs, bb, acts=None): return _fwd(F32, packed, pts, viewdirs, bb, acts)
+def mlp_fwd_f16(packed_f16, inp, viewdirs, bb, acts=None, rows24=False):
+    return _fwd(F16X3, packed_f16, inp, viewdirs, bb, acts, rows24=rows24)
+def mlp_fwd_lp(packed_lp, code, inp, viewdirs, bb, acts=None): return _fwd(LP, packed_lp, inp, viewdirs, bb, acts, code)
+def mlp_bwd(packed, packed_t, acts, g_out, out=None): return _bwd(F32, packed, packed_t, acts, g_out, out)
+def mlp_bwd_f16(packed, packed_t_f16, acts, g_out, wgrad_f16=True, out=None):
+    return _bwd(F16X3, packed, packed_t_f16, acts, g_out, out, wgrad_f16=wgrad_f16)
+def mlp_bwd_lp(packed, packed_t_lp, code, acts, g_out, out=None):
+    return _bwd(LP, packed, packed_t_lp, acts, g_out, out, code)
+def mlp_bwd2(packed, packed_t, acts, g_out, outs, after_first=None, defer=False):
+    return _bwd_pair(F32, packed, packed_t, acts, g_out, outs, after_first=after_first, defer=defer)
+def mlp_bwd_f16_2(packed, packed_t_f16, acts, g_out, outs, defer=False):
+    return _bwd_pair(F16X3, packed, packed_t_f16, acts, g_out, outs, wgrad_f16=True, defer=defer)
+def mlp_bwd_lp2(packed_t_lp, code, acts, g_out, outs, after_first=None, defer=False, gmax=None):
+    return _bwd_pair(LP, None, packed_t_lp, acts, g_out, outs, code, after_first=after_first, defer=defer, gmax=gmax)
 
 class CoarsePoints:
     """The static coarse-sample buffers of a graph-captured step and what the launch in front of it needs to fill them
@@ -579,64 +591,6 @@ def stage_inputs(pairs, scalar=None, tick=None, points=None, rays=None, packs=No
 
 def lp_point_tiles(P: int) -> int:
     return int(_lib.load().scade_mlp_lp_point_tiles(int(P)))
-
-
-def mlp_fwd_lp(packed_lp: Tensor, code: int, inp: Tensor, viewdirs: Optional[Tensor],
-               bb: Optional[Tensor], acts: Optional[Tensor] = None) -> Tensor:
-    """16-bit-operand forward: inp [P,60] (viewdirs None) or pts [N,S,3] + viewdirs [N,3] + bb [4].  ``code``: the
-    format code of LP_FORMATS (0 = f16, 1 = bf16, 2 = bf16-s8; the blob must be bf16 for codes 1 and 2)."""
-    check(inp, "mlp_fwd_lp: input")
-    inp = _c(inp)
-    if viewdirs is None:
-        if inp.dim() != 2 or inp.shape[1] != 60:
-            raise ValueError("mlp_fwd_lp: x must be [P,60]")
-        P = inp.shape[0]
-        out = torch.empty(P, 4, device=inp.device, dtype=torch.float32)
-        call("scade_mlp_fwd_lp", ptr(packed_lp), int(code), 0, ptr(inp), None, 0, None, P, 1, ptr(out), ptr(acts),
-             stream())
-        return out
-    N, S = inp.shape[0], inp.shape[1]
-    viewdirs, vstride = _rows(viewdirs, "mlp_fwd_lp: viewdirs")
-    bb = _c(check(bb, "mlp_fwd_lp: bb"))
-    out = torch.empty(N, S, 4, device=inp.device, dtype=torch.float32)
-    t0 = KERNEL_TIMER.start() if KERNEL_TIMER is not None else None
-    call("scade_mlp_fwd_lp", ptr(packed_lp), int(code), 1, ptr(inp), ptr(viewdirs), vstride, ptr(bb), N * S, S,
-         ptr(out), ptr(acts), stream())
-    if t0 is not None:
-        KERNEL_TIMER.stop("mlp_fwd_lp_kernel", t0, float(N * S) * MLP_FLOP_PER_POINT)
-    return out
-
-
-def mlp_fwd_embedded(packed: Tensor, x: Tensor, acts: Optional[Tensor] = None) -> Tensor:
-    """NeRF.forward on x[P,60] (mode 0)."""
-    check(x, "mlp_fwd: x")
-    if x.dim() != 2 or x.shape[1] != 60:
-        raise ValueError(f"mlp_fwd: x must be [P,60], got {tuple(x.shape)}")
-    x = _c(x)
-    P = x.shape[0]
-    out = torch.empty(P, 4, device=x.device, dtype=torch.float32)
-    call("scade_mlp_fwd", ptr(packed), 0, ptr(x), None, 0, None, P, 1, ptr(out), ptr(acts), stream())
-    return out
-
-
-def mlp_fwd_points(packed: Tensor, pts: Tensor, viewdirs: Tensor, bb: Tensor,
-                   acts: Optional[Tensor] = None) -> Tensor:
-    """run_network fused (mode 1): pts [N,S,3], viewdirs [N,3], bb [4] -> raw [N,S,4]."""
-    check(pts, "mlp_fwd: pts"); check(viewdirs, "mlp_fwd: viewdirs"); check(bb, "mlp_fwd: bb")
-    if pts.dim() != 3 or pts.shape[-1] != 3:
-        raise ValueError(f"mlp_fwd: pts must be [N,S,3], got {tuple(pts.shape)}")
-    N, S = pts.shape[0], pts.shape[1]
-    if tuple(viewdirs.shape) != (N, 3):
-        raise ValueError(f"mlp_fwd: viewdirs must be [{N},3], got {tuple(viewdirs.shape)}")
-    viewdirs, vstride = _rows(viewdirs, "mlp_fwd: viewdirs")
-    pts, bb = _c(pts), _c(bb)
-    out = torch.empty(N, S, 4, device=pts.device, dtype=torch.float32)
-    t0 = KERNEL_TIMER.start() if KERNEL_TIMER is not None else None
-    call("scade_mlp_fwd", ptr(packed), 1, ptr(pts), ptr(viewdirs), vstride, ptr(bb), N * S, S,
-         ptr(out), ptr(acts), stream())
-    if t0 is not None:
-        KERNEL_TIMER.stop("mlp_fwd_kernel", t0, float(N * S) * MLP_FLOP_PER_POINT)
-    return out
 
 
 def embed(x: Tensor, multires: int) -> Tensor:

@@ -251,10 +251,7 @@ class NeRF(nn.Module):
         return self.inference_precision != "f32" and not train
 
     def _fast_forward(self, inp, viewdirs, bb):
-        if self.inference_precision == "f16x3":
-            return ops.mlp_fwd_f16(self.packed_f16(), inp, viewdirs, bb)
-        code, bf16 = ops.LP_FORMATS[self.inference_precision]
-        return ops.mlp_fwd_lp(self.packed_lp(bf16), code, inp, viewdirs, bb)
+        return ops.mlp_fwd_net(self, ops.TRAIN_FORMATS[self.inference_precision], inp, viewdirs, bb)
 
     def forward(self, x):
         """x [P, 60] = [gamma(pts) | viewdir] -> [P,4] (helpers:223-247)."""
